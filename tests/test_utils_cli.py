@@ -44,11 +44,25 @@ def test_bench_json_contract(tmp_path):
     repo = os.path.join(os.path.dirname(__file__), "..")
     out = subprocess.run(
         [sys.executable, "bench.py", "--steps", "1", "--warmup", "0",
-         "--local-epochs", "1"],
+         "--local-epochs", "1", "--dump-outputs", str(tmp_path / "dump")],
         cwd=repo, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     line = out.stdout.strip().splitlines()[-1]
     d = json.loads(line)
+    assert "phase_ms_per_step" not in d  # only with --full
+    # --dump-outputs: the last timed round's outputs as float .npy arrays
+    import numpy as np
+    from hefl.config import preset
+    from hefl.models import build_model
+    dumped = {f[:-4]: np.load(tmp_path / "dump" / f)
+              for f in os.listdir(tmp_path / "dump")}
+    assert set(dumped) == {"weights", "train_loss", "train_acc"}
+    assert all(a.dtype in (np.float32, np.float64) for a in dumped.values())
+    assert dumped["weights"].shape == (
+        build_model(preset("config2").model).n_params(),)
+    assert np.isfinite(dumped["weights"]).all()
+    assert dumped["train_loss"].shape == (1,) and dumped["train_loss"][0] > 0
+    assert 0.0 <= dumped["train_acc"][0] <= 1.0
     assert d["metric"] == "fl_rounds_per_sec"
     assert d["unit"] == "rounds/s" and d["higher_is_better"] is True
     assert d["scaling"] == "weak" and d["n_gpus"] == 1
@@ -75,15 +89,21 @@ def test_bench_two_rank_driver_invocation():
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", str(__import__("conftest").free_port()), "bench.py", "--gpus", "2",
-         "--steps", "1", "--warmup", "0", "--local-epochs", "1"],
+         "--steps", "1", "--warmup", "0", "--local-epochs", "1", "--full"],
         cwd=repo, capture_output=True, text=True, timeout=600,
-        env=dict(os.environ, MASTER_ADDR="127.0.0.1"))
+        # CPU/gloo on every machine: with GPUs visible the ranks would pick
+        # nccl and need one device each, which a 1-GPU box cannot give
+        env=dict(os.environ, MASTER_ADDR="127.0.0.1",
+                 HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1"))
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak"
     assert d["config"]["global_batch"] == 64
     assert d["config"]["parallelism"].startswith("fl-dp2")
+    # --full adds the per-phase breakdown of the timed rounds
+    assert set(d["phase_ms_per_step"]) == {"local_train", "fedavg"}
+    assert sum(d["phase_ms_per_step"].values()) <= d["ms_per_step"] * 1.001
 
 
 def test_cli_checkpoint_resume(tmp_path):
