@@ -33,6 +33,13 @@ def main():
                     default=None,
                     help="training augmentation ('full' = the reference's "
                          "shear 0.2 / zoom 0.2 / h-flip set)")
+    ap.add_argument("--key-mode", choices=["shared", "threshold"],
+                    default=None,
+                    help="'threshold': n-of-n key shares, no client ever "
+                         "holds the secret key (default: shared keypair)")
+    ap.add_argument("--smudge-bits", type=int, default=None, metavar="N",
+                    help="threshold decryption smudging-noise width, 0..48 "
+                         "(default 16)")
     ap.add_argument("--callbacks", action="store_true",
                     help="enable EarlyStopping/ReduceLROnPlateau per client")
     ap.add_argument("--checkpoint", default=None, metavar="PATH",
@@ -54,6 +61,10 @@ def main():
         cfg.fl.encrypted = False
     if args.augment is not None:
         cfg.fl.augment = args.augment
+    if args.key_mode is not None:
+        cfg.fl.key_mode = args.key_mode
+    if args.smudge_bits is not None:
+        cfg.fl.smudge_bits = args.smudge_bits
     device = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
 
     init_distributed()

@@ -77,6 +77,11 @@ class FLConfig:
     # FLPyfhelin.py:80-86 — applied in the data generator)
     augment: str = "none"
     seed: int = 1234
+    # "shared": one keypair, sk on every rank (the reference's model);
+    # "threshold": n-of-n additive key shares, no party ever holds the
+    # secret key (hefl/fl/secure.py)
+    key_mode: str = "shared"
+    smudge_bits: int = 16                 # threshold decryption smudging noise width
 
 
 @dataclass

@@ -38,6 +38,12 @@ std::vector<torch::Tensor> ct_mul(torch::Tensor a, torch::Tensor b,
 std::vector<torch::Tensor> ks_inner(torch::Tensor dig, torch::Tensor rlk,
                                     torch::Tensor qs, torch::Tensor ratios,
                                     int64_t D, int64_t Lp, int64_t n);
+torch::Tensor uniform_center_rns(torch::Tensor bits, int64_t smudge_bits,
+                                 torch::Tensor qs, torch::Tensor ratios,
+                                 int64_t L);
+torch::Tensor pdec_share(torch::Tensor ct, torch::Tensor s_hat,
+                         torch::Tensor e_hat, bool add_c0, torch::Tensor qs,
+                         torch::Tensor ratios);
 
 // fft.hip
 torch::Tensor fft_encode(torch::Tensor vals, torch::Tensor tw_enc,
@@ -143,6 +149,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "[.., n] -> [.., L, n] center + per-limb Barrett reduce");
     m.def("ct_mul", &ct_mul, "fused ct x ct tensor product (d0, d1, d2)");
     m.def("ks_inner", &ks_inner, "fused key-switch digit inner product");
+    m.def("uniform_center_rns", &uniform_center_rns,
+          "64-bit draws [.., n] -> smudging noise residues [.., L, n]");
+    m.def("pdec_share", &pdec_share,
+          "threshold decryption share c1*s + e (+ c0) over [.., 2, L, n]");
     m.def("fft_encode", &fft_encode,
           "CKKS special-FFT encode: f64 slots -> int64 coeffs");
     m.def("fft_decode", &fft_decode,

@@ -817,6 +817,111 @@ __global__ void cbd21_kernel(const int64_t* __restrict__ bits,
     }
 }
 
+// ---------------------------------------------------------------------------
+// Threshold (n-of-n) decryption kernels (hefl/fl/secure.py, key_mode=
+// "threshold"). Both move V consecutive coefficients per thread: V = 2 is
+// one 16-byte load/store per operand, V = 1 the scalar fallback for odd n
+// or unaligned storage. A V-group never straddles a limb row (n % V == 0).
+// ---------------------------------------------------------------------------
+
+template <int V>
+struct I64Vec;
+template <>
+struct I64Vec<1> {
+    int64_t v[1];
+};
+template <>
+struct alignas(16) I64Vec<2> {
+    int64_t v[2];
+};
+
+// Smudging noise: one uniform 64-bit draw per coefficient ->
+//   v = (bits & (2^(sb+1) - 1)) - 2^sb   in [-2^sb, 2^sb),
+//   out[r, l, j] = v mod q_l in [0, q_l)  (Barrett: |v| <= 2^48 can exceed a
+// 20-bit limb prime). One launch replaces the mask / subtract elementwise
+// chain plus a bcast_center_mod launch.
+template <int V>
+__global__ void uniform_center_rns_kernel(const int64_t* __restrict__ bits,
+                                          int64_t* __restrict__ out,
+                                          int64_t total_vec, int64_t n, int L,
+                                          int sb,
+                                          const int64_t* __restrict__ qs,
+                                          const int64_t* __restrict__ ratios) {
+    using Vec = I64Vec<V>;
+    const int64_t Ln = (int64_t)L * n;
+    const uint64_t mask = (2ull << sb) - 1;
+    const int64_t half = (int64_t)(1ull << sb);
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+         t < total_vec; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = t * V;
+        const int64_t j = o % n;
+        const int l = (int)((o / n) % L);
+        const int64_t row = o / Ln;
+        const uint64_t q = (uint64_t)qs[l];
+        const uint64_t r0 = (uint64_t)ratios[2 * l];
+        const uint64_t r1 = (uint64_t)ratios[2 * l + 1];
+        const Vec x = *reinterpret_cast<const Vec*>(bits + row * n + j);
+        Vec y;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int64_t v = (int64_t)((uint64_t)x.v[k] & mask) - half;
+            const uint64_t m = v < 0 ? (uint64_t)(-v) : (uint64_t)v;
+            const uint64_t red = barrett_red128(m, 0, q, r0, r1);
+            y.v[k] = (int64_t)((v < 0 && red) ? q - red : red);
+        }
+        *reinterpret_cast<Vec*>(out + o) = y;
+    }
+}
+
+// Decryption share h = c1 * s_hat + e_hat (+ c0 for the lead party) mod q.
+// ct is [R, 2, L, n] and c0 / c1 are read in place by index arithmetic (no
+// slice copies); s_hat [>= L, n] is broadcast over R; e_hat, out are
+// [R, L, n]. All inputs are residues in [0, q): the sum is < 3q < 2^62, so
+// two conditional subtracts bring it back to [0, q).
+template <int V>
+__global__ void pdec_share_kernel(const int64_t* __restrict__ ct,
+                                  const int64_t* __restrict__ s_hat,
+                                  const int64_t* __restrict__ e_hat,
+                                  int64_t* __restrict__ out,
+                                  int64_t total_vec, int64_t n, int L,
+                                  int add_c0,
+                                  const int64_t* __restrict__ qs,
+                                  const int64_t* __restrict__ ratios) {
+    using Vec = I64Vec<V>;
+    const int64_t Ln = (int64_t)L * n;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+         t < total_vec; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = t * V;
+        const int l = (int)((o / n) % L);
+        const int64_t row = o / Ln;
+        const int64_t inner = o % Ln;
+        const uint64_t q = (uint64_t)qs[l];
+        const uint64_t r0 = (uint64_t)ratios[2 * l];
+        const uint64_t r1 = (uint64_t)ratios[2 * l + 1];
+        const int64_t ic0 = row * 2 * Ln + inner;
+        const Vec c1 = *reinterpret_cast<const Vec*>(ct + ic0 + Ln);
+        const Vec s = *reinterpret_cast<const Vec*>(s_hat + inner);
+        const Vec e = *reinterpret_cast<const Vec*>(e_hat + o);
+        Vec c0;
+        if (add_c0) c0 = *reinterpret_cast<const Vec*>(ct + ic0);
+        Vec h;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            uint64_t v = mulmod_barrett((uint64_t)c1.v[k], (uint64_t)s.v[k], q,
+                                        r0, r1) + (uint64_t)e.v[k];
+            if (add_c0) v += (uint64_t)c0.v[k];
+            if (v >= q) v -= q;
+            if (v >= q) v -= q;
+            h.v[k] = (int64_t)v;
+        }
+        *reinterpret_cast<Vec*>(out + o) = h;
+    }
+}
+
+inline bool aligned16(const void* p) {
+    return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
+}
+
 int64_t shoup_of(uint64_t w, uint64_t q) {
     unsigned __int128 t = ((unsigned __int128)w) << 64;
     return (int64_t)(uint64_t)(t / q);
@@ -1165,5 +1270,100 @@ torch::Tensor bcast_center_mod(torch::Tensor x, int64_t qc, torch::Tensor qs,
                        at::cuda::getCurrentCUDAStream(), x.data_ptr<int64_t>(),
                        out.data_ptr<int64_t>(), total, n, (int)L, (uint64_t)qc,
                        qs.data_ptr<int64_t>(), ratios.data_ptr<int64_t>());
+    return out;
+}
+
+// bits [..., n] (uniform 64-bit draws) -> out [..., L, n]: smudging noise
+// uniform in [-2^sb, 2^sb) reduced into the first L limb primes.
+torch::Tensor uniform_center_rns(torch::Tensor bits, int64_t smudge_bits,
+                                 torch::Tensor qs, torch::Tensor ratios,
+                                 int64_t L) {
+    CHECK_CUDA_OK(bits);
+    CHECK_CUDA_OK(qs);
+    CHECK_CUDA_OK(ratios);
+    TORCH_CHECK(bits.is_contiguous() && bits.dtype() == torch::kInt64);
+    TORCH_CHECK(qs.is_contiguous() && ratios.is_contiguous());
+    TORCH_CHECK(bits.dim() >= 1 && bits.size(-1) >= 1);
+    TORCH_CHECK(smudge_bits >= 0 && smudge_bits <= 48,
+                "smudge_bits must be in [0, 48]");
+    TORCH_CHECK(L >= 1 && qs.numel() >= L && ratios.numel() >= 2 * L,
+                "limb count exceeds the prime table");
+    const int64_t n = bits.size(-1);
+    auto sizes = bits.sizes().vec();
+    sizes.insert(sizes.end() - 1, L);
+    auto out = torch::empty(sizes, bits.options());
+    const int64_t total = out.numel();
+    if (total == 0) return out;
+    auto stream = at::cuda::getCurrentCUDAStream();
+    const bool vec2 = n % 2 == 0 && aligned16(bits.data_ptr<int64_t>()) &&
+                      aligned16(out.data_ptr<int64_t>());
+    const int64_t tv = vec2 ? total / 2 : total;
+    int blocks = (int)std::min<int64_t>((tv + kThreads - 1) / kThreads, 4096);
+    if (vec2) {
+        hipLaunchKernelGGL(uniform_center_rns_kernel<2>, dim3(blocks),
+                           dim3(kThreads), 0, stream,
+                           bits.data_ptr<int64_t>(), out.data_ptr<int64_t>(),
+                           tv, n, (int)L, (int)smudge_bits,
+                           qs.data_ptr<int64_t>(), ratios.data_ptr<int64_t>());
+    } else {
+        hipLaunchKernelGGL(uniform_center_rns_kernel<1>, dim3(blocks),
+                           dim3(kThreads), 0, stream,
+                           bits.data_ptr<int64_t>(), out.data_ptr<int64_t>(),
+                           tv, n, (int)L, (int)smudge_bits,
+                           qs.data_ptr<int64_t>(), ratios.data_ptr<int64_t>());
+    }
+    return out;
+}
+
+// ct [..., 2, L, n], s_hat [>= L, n], e_hat [..., L, n] -> share [..., L, n].
+torch::Tensor pdec_share(torch::Tensor ct, torch::Tensor s_hat,
+                         torch::Tensor e_hat, bool add_c0, torch::Tensor qs,
+                         torch::Tensor ratios) {
+    CHECK_CUDA_OK(ct);
+    CHECK_CUDA_OK(s_hat);
+    CHECK_CUDA_OK(e_hat);
+    CHECK_CUDA_OK(qs);
+    CHECK_CUDA_OK(ratios);
+    TORCH_CHECK(ct.is_contiguous() && s_hat.is_contiguous() &&
+                e_hat.is_contiguous() && qs.is_contiguous() &&
+                ratios.is_contiguous());
+    TORCH_CHECK(ct.dtype() == torch::kInt64 && s_hat.dtype() == torch::kInt64 &&
+                e_hat.dtype() == torch::kInt64);
+    TORCH_CHECK(ct.dim() >= 3 && ct.size(-3) == 2, "ct must be [.., 2, L, n]");
+    const int64_t L = ct.size(-2);
+    const int64_t n = ct.size(-1);
+    TORCH_CHECK(L >= 1 && n >= 1);
+    TORCH_CHECK(s_hat.dim() == 2 && s_hat.size(0) >= L && s_hat.size(1) == n,
+                "s_hat must be [>= L, n]");
+    TORCH_CHECK(qs.numel() >= L && ratios.numel() >= 2 * L,
+                "limb count exceeds the prime table");
+    auto sizes = ct.sizes().vec();
+    sizes.erase(sizes.end() - 3);  // drop the (c0, c1) dim
+    TORCH_CHECK(e_hat.sizes().vec() == sizes, "e_hat must be [.., L, n]");
+    auto out = torch::empty(sizes, ct.options());
+    const int64_t total = out.numel();
+    if (total == 0) return out;
+    auto stream = at::cuda::getCurrentCUDAStream();
+    const bool vec2 = n % 2 == 0 && aligned16(ct.data_ptr<int64_t>()) &&
+                      aligned16(s_hat.data_ptr<int64_t>()) &&
+                      aligned16(e_hat.data_ptr<int64_t>()) &&
+                      aligned16(out.data_ptr<int64_t>());
+    const int64_t tv = vec2 ? total / 2 : total;
+    int blocks = (int)std::min<int64_t>((tv + kThreads - 1) / kThreads, 4096);
+    if (vec2) {
+        hipLaunchKernelGGL(pdec_share_kernel<2>, dim3(blocks), dim3(kThreads),
+                           0, stream, ct.data_ptr<int64_t>(),
+                           s_hat.data_ptr<int64_t>(), e_hat.data_ptr<int64_t>(),
+                           out.data_ptr<int64_t>(), tv, n, (int)L,
+                           add_c0 ? 1 : 0, qs.data_ptr<int64_t>(),
+                           ratios.data_ptr<int64_t>());
+    } else {
+        hipLaunchKernelGGL(pdec_share_kernel<1>, dim3(blocks), dim3(kThreads),
+                           0, stream, ct.data_ptr<int64_t>(),
+                           s_hat.data_ptr<int64_t>(), e_hat.data_ptr<int64_t>(),
+                           out.data_ptr<int64_t>(), tv, n, (int)L,
+                           add_c0 ? 1 : 0, qs.data_ptr<int64_t>(),
+                           ratios.data_ptr<int64_t>());
+    }
     return out;
 }

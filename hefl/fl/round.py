@@ -43,7 +43,9 @@ class FLRunner:
             ctx = CKKSContext(cfg.he, device=device)
             self.agg = SecureAggregator(ctx, rank=self.rank, verbose=verbose,
                                         denom_mode=cfg.fl.denom_mode,
-                                        n_clients=cfg.fl.n_clients)
+                                        n_clients=cfg.fl.n_clients,
+                                        key_mode=cfg.fl.key_mode,
+                                        smudge_bits=cfg.fl.smudge_bits)
 
     def run_round(self, epochs: Optional[int] = None) -> FLRoundResult:
         t0 = time.perf_counter()

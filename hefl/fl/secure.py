@@ -15,14 +15,58 @@ add/mult loop (:366-390, timed at 231 s for 2 clients) — into:
   3. one modreduce kernel back to [0, q_i), one ct x plain(1/n) multiply,
      one rescale — run for EVERY n including n=1, so a 1-GPU round is
      structurally identical to the 8-GPU round minus the collective,
-  4. decrypt (key-holder only; the aggregation itself used no key at all,
-     preserving the reference's pk-only-server model, FLPyfhelin.py:370).
+  4. decrypt. The aggregation itself used no key at all, preserving the
+     reference's pk-only-server model (FLPyfhelin.py:370); who can decrypt
+     depends on the key mode below.
 
-Key agreement: the reference shares ONE keypair via pickle files (cell 1 +
-FLPyfhelin.py:346-355). Here rank 0's keys are broadcast over the process
-group at init — correctness no longer depends on every rank seeding keygen
-identically (with he.seed=None each rank's keygen draws OS entropy; summing
-ciphertexts under different keys would decrypt to noise with no error).
+Key agreement, key_mode="shared" (default): the reference shares ONE keypair
+via pickle files (cell 1 + FLPyfhelin.py:346-355). Here rank 0's keys are
+broadcast over the process group at init — correctness no longer depends on
+every rank seeding keygen identically (with he.seed=None each rank's keygen
+draws OS entropy; summing ciphertexts under different keys would decrypt to
+noise with no error).
+
+Key separation: in shared mode EVERY rank holds sk, so any client can decrypt
+any other client's ciphertext, including the partial sums it sees during the
+ring all-reduce. That is the reference's trust model (one privatekey.pickle
+read by everybody), not a privacy property. key_mode="threshold" removes it.
+
+Key agreement, key_mode="threshold": n-of-n additive threshold CKKS, semi-
+honest parties, k <= 8 parties so the lazy int64 sums below cannot overflow.
+All arithmetic is per RNS limb, NTT domain, mod q:
+
+  common polynomial   a uniform [L, n], public; rank 0 samples it and
+                      broadcasts it (single-process simulation: sampled once)
+  party i key share   s_i ternary, e_i error (keygen's distributions), drawn
+                      from a per-party stream (seed + party index, or OS
+                      entropy) — the shared-seed keygen stream is identical
+                      on every rank and would give every party the same s_i;
+                      b_i = -(a*s_i + e_i);  party i keeps only s_i
+  collective pk       b = sum_i b_i  (int64 SUM all-reduce + modreduce; eight
+                      residues < 2^60 cannot overflow),  pk = (b, a).
+                      The secret s = sum_i s_i exists nowhere. Encryption and
+                      aggregation run unchanged under pk.
+  decryption share    on the aggregated ct = (c0, c1) at Lc limbs:
+                      h_i = c1*s_i + NTT(e'_i) (+ c0 for the lead party,
+                      rank 0), e'_i fresh smudging noise uniform in
+                      [-2^smudge_bits, 2^smudge_bits) per coefficient, drawn
+                      anew for every decryption from the party's own
+                      reseeded RNG
+  combine             pt = modreduce(sum_i h_i)  (int64 SUM all-reduce: each
+                      h_i < q < 2^60, eight of them < 2^63), then decode.
+
+After aggregation every rank holds the same averaged ciphertext, so that one
+extra all-reduce of shares yields the plaintext mean on every rank. A single
+share decodes to noise: no rank can decrypt alone, neither another client's
+upload nor a partial sum.
+
+smudge_bits trades statistical hiding of the decryption noise (which depends
+on the ciphertext's noise, hence on s) against precision: worst-case slot
+error added k*n*2^smudge_bits/scale, typically 2^smudge_bits*sqrt(k*n/3)/scale
+(~3e-5 at n=8192, scale 2^40, k=8, the default 16). Valid range 0..48. It is
+a tunable, NOT a proof of simulation security. Collective relinearisation-key
+generation is out of scope, so threshold mode excludes the encrypted
+denominator (ct x ct); t-of-n thresholds and malicious parties are too.
 
 The timing labels mirror the reference's prints (FLPyfhelin.py:224,267,389)
 for log familiarity.
@@ -36,7 +80,7 @@ from typing import Dict, Optional
 import torch
 import torch.distributed as dist
 
-from ..he.ckks import CKKSContext, CtxtTensor, KeyPair
+from ..he.ckks import CKKSContext, CtxtTensor, KeyPair, check_smudge_bits
 
 # Per-slab payload for the bucketed all-reduce. xGMI is 7 point-to-point
 # links x ~153 GB/s per GPU; ~64 MiB slabs are big enough to amortize ring
@@ -53,15 +97,18 @@ class AggStats:
 class SecureAggregator:
     """Per-rank helper owning the CKKS context + keys for encrypted FedAvg.
 
-    Rank 0 generates the keypair (and relin keys / encrypted denominator if
-    configured) and broadcasts it; every other rank adopts it. Encryption
-    randomness is then re-seeded per rank so client ciphertexts are
-    independent.
+    key_mode="shared": rank 0 generates the keypair (and relin keys /
+    encrypted denominator if configured) and broadcasts it; every other rank
+    adopts it. key_mode="threshold": the ranks run the collective keygen of
+    the module docstring and `keys.sk` holds only this rank's share. Either
+    way encryption randomness is then re-seeded per rank so client
+    ciphertexts are independent.
     """
 
     def __init__(self, ctx: CKKSContext, rank: int = 0, verbose: bool = False,
                  denom_mode: str = "plain", n_clients: Optional[int] = None,
-                 bucket_bytes: int = DEFAULT_BUCKET_BYTES):
+                 bucket_bytes: int = DEFAULT_BUCKET_BYTES,
+                 key_mode: str = "shared", smudge_bits: int = 16):
         """denom_mode:
         - "plain":     divide the summed ciphertext by plaintext 1/n
                        (ct x plain mult + rescale — what the reference
@@ -70,13 +117,28 @@ class SecureAggregator:
                        rescale — the reference's commented-out intent,
                        c_denom at FLPyfhelin.py:371; BASELINE.json config #3).
                        Requires n_clients at construction.
+        key_mode: "shared" | "threshold" (module docstring); smudge_bits is
+        the threshold-decryption noise width, 0..48.
         """
         assert denom_mode in ("plain", "encrypted")
+        if key_mode not in ("shared", "threshold"):
+            raise ValueError(
+                f"key_mode must be 'shared' or 'threshold', got {key_mode!r}")
+        check_smudge_bits(smudge_bits)
+        if key_mode == "threshold" and denom_mode == "encrypted":
+            raise ValueError(
+                "key_mode='threshold' cannot use denom_mode='encrypted': "
+                "collective relinearisation-key generation is not implemented")
         self.ctx = ctx
-        self.keys: KeyPair = ctx.keygen()
+        self.rank = rank
+        self.key_mode = key_mode
+        self.smudge_bits = smudge_bits
         self.denom_mode = denom_mode
         self.bucket_bytes = bucket_bytes
         self.enc_denom = None
+        # threshold mode never runs the full keygen: no sk to begin with
+        self.keys: Optional[KeyPair] = (
+            ctx.keygen() if key_mode == "shared" else None)
         if denom_mode == "encrypted":
             if ctx.L < 3:
                 raise ValueError(
@@ -94,8 +156,13 @@ class SecureAggregator:
         self.stats = AggStats()
 
     def _sync_keys(self) -> None:
-        """Broadcast rank 0's key material so all ranks share ONE keypair
-        (the reference's single publickey.pickle/privatekey.pickle model)."""
+        """Shared mode: broadcast rank 0's key material so all ranks share
+        ONE keypair (the reference's single publickey.pickle /
+        privatekey.pickle model). Threshold mode: the collective keygen —
+        no secret material is ever sent."""
+        if self.key_mode == "threshold":
+            self.keys = self._threshold_keygen()
+            return
         if not (dist.is_initialized() and dist.get_world_size() > 1):
             return
         dist.broadcast(self.keys.sk, src=0)
@@ -105,15 +172,34 @@ class SecureAggregator:
         if self.enc_denom is not None:
             dist.broadcast(self.enc_denom.data, src=0)
 
+    def _threshold_keygen(self) -> KeyPair:
+        """Collective keygen: broadcast a, all-reduce the b_i. Only public
+        values cross the wire; the returned sk is this rank's share alone.
+        World size 1 runs the same sequence without the collectives."""
+        ctx = self.ctx
+        world = dist.get_world_size() if dist.is_initialized() else 1
+        assert world <= 8, "lazy int64 reduction is proven for <= 8 summands"
+        a = ctx.sample_crp()
+        if world > 1:
+            dist.broadcast(a, src=0)
+        share = ctx.keygen_share(a, self.rank)
+        b_sum = share.b_share.clone()
+        if world > 1:
+            dist.all_reduce(b_sum, op=dist.ReduceOp.SUM)
+        return KeyPair(sk=share.sk_share, pk=ctx.combine_pk(b_sum, a))
+
     def _t(self, label: str, t0: float):
         dt = time.perf_counter() - t0
         self.stats.seconds[label] = self.stats.seconds.get(label, 0.0) + dt
         if self.verbose:
             print(f"Time to {label}:", dt)
 
-    def _slab_cts(self) -> int:
-        """Ciphertexts per all-reduce bucket (>=1)."""
-        per_ct = 2 * self.ctx.L * self.ctx.n * 8  # int64 bytes
+    def _slab_cts(self, polys: Optional[int] = None) -> int:
+        """Ciphertexts per all-reduce bucket (>=1). `polys` = limb rows per
+        item: 2*L for a fresh ciphertext (default), Lc for a decryption
+        share."""
+        polys = 2 * self.ctx.L if polys is None else polys
+        per_ct = polys * self.ctx.n * 8  # int64 bytes
         return max(1, self.bucket_bytes // per_ct)
 
     def encrypt(self, vec: torch.Tensor) -> CtxtTensor:
@@ -194,9 +280,30 @@ class SecureAggregator:
 
     def decrypt(self, ct: CtxtTensor) -> torch.Tensor:
         t0 = time.perf_counter()
-        vec = self.ctx.decrypt_tensor(ct, self.keys.sk)
+        if self.key_mode == "threshold":
+            vec = self._threshold_decrypt(ct)
+        else:
+            vec = self.ctx.decrypt_tensor(ct, self.keys.sk)
         self._t("decrypt", t0)
         return vec
+
+    def _threshold_decrypt(self, ct: CtxtTensor) -> torch.Tensor:
+        """This rank's share of the (identical on every rank) aggregated
+        ciphertext, a bucketed lazy int64 all-reduce of the shares, combine.
+        A ResNet-size share tensor is hundreds of MB, hence the buckets."""
+        world = dist.get_world_size() if dist.is_initialized() else 1
+        assert world <= 8, "lazy int64 reduction is proven for <= 8 summands"
+        share = self.ctx.partial_decrypt_tensor(
+            ct, self.keys.sk, self.smudge_bits,
+            lead=self.rank == 0 or world == 1)
+        if world > 1:
+            slab = self._slab_cts(ct.level)
+            works = [dist.all_reduce(share[i:i + slab], op=dist.ReduceOp.SUM,
+                                     async_op=True)
+                     for i in range(0, share.shape[0], slab)]
+            for w in works:
+                w.wait()
+        return self.ctx.combine_shares_tensor(share, ct.scale, ct.count)
 
     def fedavg(self, vec: torch.Tensor, n_clients: Optional[int] = None) -> torch.Tensor:
         """Full encrypted FedAvg of a flat fp32 weight vector."""

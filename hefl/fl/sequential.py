@@ -9,7 +9,9 @@ reference's client i+1 silently continued from client i's weights because the
 
 The multi-process path (1 GPU = 1 client over RCCL) is hefl/fl/round.py;
 this module is the 1-device simulation, the CLI driver and the e2e
-accuracy-parity harness.
+accuracy-parity harness. With fl.key_mode="threshold" it holds one key share
+per simulated client and decrypts by summing their partial decryptions — the
+same protocol as the multi-process path, runnable on a single device.
 """
 from __future__ import annotations
 
@@ -21,7 +23,8 @@ import torch
 
 from ..config import RunConfig
 from ..data.synthetic import SyntheticMedicalImages
-from ..he.ckks import CKKSContext, CtxtTensor
+from ..he.ckks import (CKKSContext, CtxtTensor, KeyPair, KeyShare,
+                       check_smudge_bits)
 from ..models import build_model
 from .callbacks import EarlyStopping, ModelCheckpoint, ReduceLROnPlateau
 from .client import LocalClient
@@ -51,7 +54,24 @@ class SequentialFL:
                         for i in range(cfg.fl.n_clients)]
         self.ctx: Optional[CKKSContext] = None
         self.keys = None
-        if cfg.fl.encrypted:
+        self.key_shares: Optional[List[KeyShare]] = None
+        if cfg.fl.key_mode not in ("shared", "threshold"):
+            raise ValueError("key_mode must be 'shared' or 'threshold', "
+                             f"got {cfg.fl.key_mode!r}")
+        if cfg.fl.encrypted and cfg.fl.key_mode == "threshold":
+            # n-of-n threshold keys (hefl/fl/secure.py): one share per
+            # simulated client plus the collective pk; keys.sk stays None,
+            # the sum of the s_i is never formed
+            check_smudge_bits(cfg.fl.smudge_bits)
+            assert cfg.fl.n_clients <= 8, \
+                "lazy int64 share sum is proven for <= 8 clients"
+            self.ctx = CKKSContext(cfg.he, device=device)
+            a = self.ctx.sample_crp()
+            self.key_shares = [self.ctx.keygen_share(a, i)
+                               for i in range(cfg.fl.n_clients)]
+            b_sum = torch.stack([s.b_share for s in self.key_shares]).sum(0)
+            self.keys = KeyPair(sk=None, pk=self.ctx.combine_pk(b_sum, a))
+        elif cfg.fl.encrypted:
             self.ctx = CKKSContext(cfg.he, device=device)
             self.keys = self.ctx.keygen()
         # held-out test set (reference: 400 test images, notebook cell 0/3):
@@ -107,7 +127,18 @@ class SequentialFL:
                     agg.data + ct.data, agg.scale, agg.count)
             self.ctx.modreduce_tensor_(agg)
             avg = self.ctx.rescale_tensor(self.ctx.mul_scalar_tensor(agg, 1.0 / n))
-            new_g = self.ctx.decrypt_tensor(avg, self.keys.sk).to(self.device)
+            if self.key_shares is not None:
+                # the round's decryption is the sum of the k partial shares
+                # (party 0 leads: its share carries c0)
+                acc = None
+                for i, ks in enumerate(self.key_shares):
+                    h = self.ctx.partial_decrypt_tensor(
+                        avg, ks.sk_share, self.cfg.fl.smudge_bits, lead=i == 0)
+                    acc = h if acc is None else acc.add_(h)
+                new_g = self.ctx.combine_shares_tensor(
+                    acc, avg.scale, avg.count).to(self.device)
+            else:
+                new_g = self.ctx.decrypt_tensor(avg, self.keys.sk).to(self.device)
         else:
             new_g = torch.stack(vecs).mean(0)
         load_flat_params(self.global_model, new_g)

@@ -193,6 +193,29 @@ class GpuBackend:
         return self._C.bcast_center_mod(x.contiguous(), qc, self.qs,
                                         self.ratio_words, L)
 
+    # ----- threshold decryption (hefl/fl/secure.py key_mode="threshold") -----
+    def uniform_center_rns(self, bits: torch.Tensor, smudge_bits: int,
+                           L: int) -> torch.Tensor:
+        """bits [..., n] raw 64-bit draws -> [..., L, n] residues of noise
+        uniform in [-2^smudge_bits, 2^smudge_bits). One launch."""
+        return self._C.uniform_center_rns(bits.contiguous(), int(smudge_bits),
+                                          self.qs, self.ratio_words, L)
+
+    def ntt_all_(self, x: torch.Tensor) -> torch.Tensor:
+        """In-place ntt_all for a contiguous tensor the caller owns."""
+        L = x.shape[-2]
+        self._C.ntt_limbs(x.view(-1, L, self.n), self.w, self.w_shoup,
+                          self.qs, L)
+        return x
+
+    def pdec_share(self, ct: torch.Tensor, s_hat: torch.Tensor,
+                   e_hat: torch.Tensor, add_c0: bool) -> torch.Tensor:
+        """ct [..., 2, Lc, n] -> c1*s_hat + e_hat (+ c0) [..., Lc, n], c0/c1
+        read in place (no slice copies). One launch."""
+        return self._C.pdec_share(ct.contiguous(), s_hat.contiguous(),
+                                  e_hat.contiguous(), bool(add_c0), self.qs,
+                                  self.ratio_words)
+
 
 # ---------------------------------------------------------------------------
 # Data containers
@@ -232,9 +255,31 @@ class CtxtTensor:
 
 @dataclass
 class KeyPair:
-    sk: torch.Tensor          # int64 [L, n] NTT form
+    sk: torch.Tensor          # int64 [L, n] NTT form (threshold mode: one
+                              # party's share, or None where none is held)
     pk: torch.Tensor          # int64 [2, L, n] NTT form: (b, a)
     relin: Optional[torch.Tensor] = None  # [dnum, 2, L, n] later
+
+
+@dataclass
+class KeyShare:
+    """One party's part of an n-of-n additive threshold key: the secret is
+    s = sum_i s_i, never assembled anywhere; b = sum_i b_i is public."""
+    sk_share: torch.Tensor    # int64 [L, n] NTT form, stays with the party
+    b_share: torch.Tensor     # int64 [L, n] NTT form: -(a*s_i + e_i) mod q
+
+
+# Smudging-noise width accepted by partial decryption: 2^48 keeps the noise
+# magnitude exact in int64 / f64 with room for the 60-bit limb arithmetic.
+MAX_SMUDGE_BITS = 48
+
+
+def check_smudge_bits(smudge_bits: int) -> int:
+    if not (isinstance(smudge_bits, int) and 0 <= smudge_bits <= MAX_SMUDGE_BITS):
+        raise ValueError(
+            f"smudge_bits must be an int in [0, {MAX_SMUDGE_BITS}], "
+            f"got {smudge_bits!r}")
+    return smudge_bits
 
 
 # ---------------------------------------------------------------------------
@@ -328,15 +373,17 @@ class CKKSContext:
     # Per-message encryption noise samples on the DEVICE RNG when on GPU:
     # host sampling of u/e0/e1 for a packed weight tensor costs tens of ms
     # of numpy + transfer, device sampling is microseconds.
-    def _sample_ternary(self, shape, host: bool = False) -> torch.Tensor:
+    def _sample_ternary(self, shape, host: bool = False, rng=None) -> torch.Tensor:
         # {-1, 0, 1} uniform (hamming-weight variant not needed at these n)
         if not host and self.device.type == "cuda":
             return torch.randint(-1, 2, tuple(shape), generator=self.gpu_gen,
                                  device=self.device, dtype=torch.int64)
-        v = torch.from_numpy(self._cpu_rng.integers(-1, 2, size=shape))
+        rng = self._cpu_rng if rng is None else rng
+        v = torch.from_numpy(rng.integers(-1, 2, size=shape))
         return v.to(torch.int64)
 
-    def _sample_err(self, shape, eta: int = 21, host: bool = False) -> torch.Tensor:
+    def _sample_err(self, shape, eta: int = 21, host: bool = False,
+                    rng=None) -> torch.Tensor:
         # centered binomial, sigma = sqrt(eta/2) ~= 3.24 (SEAL sigma 3.2)
         if not host and self.device.type == "cuda":
             # one uniform 64-bit draw per coefficient; the HIP kernel takes
@@ -345,8 +392,9 @@ class CKKSContext:
                                  generator=self.gpu_gen, device=self.device,
                                  dtype=torch.int64)
             return self.backend._C.cbd21(bits)
-        b = self._cpu_rng.integers(0, 2, size=(eta,) + tuple(shape)).sum(axis=0)
-        b2 = self._cpu_rng.integers(0, 2, size=(eta,) + tuple(shape)).sum(axis=0)
+        rng = self._cpu_rng if rng is None else rng
+        b = rng.integers(0, 2, size=(eta,) + tuple(shape)).sum(axis=0)
+        b2 = rng.integers(0, 2, size=(eta,) + tuple(shape)).sum(axis=0)
         return torch.from_numpy(b - b2).to(torch.int64)
 
     def _sample_uniform(self, shape_limbs) -> torch.Tensor:
@@ -387,6 +435,45 @@ class CKKSContext:
             b[i] = torch.remainder(-(as_ + ehat[i]), self._q(i))
         pk = torch.stack([b, a])                       # [2, L, n]
         return KeyPair(sk=sk, pk=pk)
+
+    # ----- n-of-n threshold keys (protocol: hefl/fl/secure.py) -----
+    def sample_crp(self) -> torch.Tensor:
+        """Common random polynomial a: uniform [L, n], NTT domain. Public;
+        one party samples it and every party uses the same one."""
+        return self._sample_uniform((self.L, self.n)).to(self.device)
+
+    def _party_rng(self, party: int):
+        """Per-party host stream for key shares. keygen's shared-seed stream
+        is identical on every rank when cfg.seed is set — shares drawn from
+        it would all be the same s_i."""
+        if self.cfg.seed is None:
+            return np.random.default_rng()
+        return np.random.default_rng([int(self.cfg.seed), 0x7368, int(party)])
+
+    def keygen_share(self, a: torch.Tensor, party: int) -> KeyShare:
+        """Party `party`'s share under the common polynomial a:
+        s_i ternary, e_i error (keygen's distributions),
+        b_i = -(a*s_i + e_i) mod q."""
+        if party < 0:
+            raise ValueError(f"party index must be >= 0, got {party}")
+        n = self.n
+        rng = self._party_rng(party)
+        s = self._sample_ternary((n,), host=True, rng=rng)
+        e = self._sample_err((n,), host=True, rng=rng)
+        sk = self._to_rns_ntt(s)                       # [L, n]
+        ehat = self._to_rns_ntt(e)
+        a = a.to(self.device)
+        b = torch.empty_like(a)
+        for i in range(self.L):
+            as_ = self.backend.modmul(a[i], sk[i], i)
+            b[i] = torch.remainder(-(as_ + ehat[i]), self._q(i))
+        return KeyShare(sk_share=sk, b_share=b)
+
+    def combine_pk(self, b_sum_lazy: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
+        """Collective public key (b, a) from the lazy int64 SUM of <= 8
+        parties' b_i (8 residues < 2^60 cannot overflow)."""
+        b = self._modreduce_(b_sum_lazy.to(self.device).clone())
+        return torch.stack([b, a.to(self.device)])     # [2, L, n]
 
     # ----- encode / decode -----
     def encode(self, vals: np.ndarray, nlimbs: Optional[int] = None,
@@ -505,6 +592,56 @@ class CKKSContext:
             out[..., i, :] = torch.remainder(c0[..., i, :] + cs, self._q(i))
         return out
 
+    def _draw_bits(self, shape) -> torch.Tensor:
+        """One uniform 64-bit draw per element from this context's (per-rank
+        reseeded) encryption stream — the same feed cbd21 gets."""
+        if self.device.type == "cuda":
+            return torch.randint(-(2 ** 63), 2 ** 63 - 1, tuple(shape),
+                                 generator=self.gpu_gen, device=self.device,
+                                 dtype=torch.int64)
+        return torch.from_numpy(self._cpu_rng.integers(
+            -(2 ** 63), 2 ** 63, size=tuple(shape), dtype=np.int64))
+
+    def partial_decrypt_data(self, ctdata: torch.Tensor, sk_share: torch.Tensor,
+                             smudge_bits: int, lead: bool,
+                             bits: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One party's decryption share of ct data [..., 2, Lc, n]:
+
+            h_i = c1 * s_i + NTT(e'_i) (+ c0 for the lead party)  mod q
+
+        with e'_i fresh smudging noise, uniform in [-2^smudge_bits,
+        2^smudge_bits) per coefficient: e' = (bits & (2^(sb+1)-1)) - 2^sb.
+        `bits` ([..., n] int64) injects the raw 64-bit draws — tests use it to
+        compare the CPU and GPU paths bit for bit; by default they are drawn
+        anew on every call. Returns [..., Lc, n]; the SUM of all parties'
+        shares, reduced mod q, is the plaintext (combine_shares_tensor)."""
+        sb = check_smudge_bits(smudge_bits)
+        nlimbs = ctdata.shape[-2]
+        lead_shape = tuple(ctdata.shape[:-3])
+        if bits is None:
+            bits = self._draw_bits(lead_shape + (self.n,))
+        elif tuple(bits.shape) != lead_shape + (self.n,):
+            raise ValueError(f"bits must have shape {lead_shape + (self.n,)}, "
+                             f"got {tuple(bits.shape)}")
+        if self.device.type == "cuda":
+            be = self.backend
+            e_hat = be.ntt_all_(be.uniform_center_rns(
+                bits.to(self.device), sb, nlimbs))
+            return be.pdec_share(ctdata, sk_share, e_hat, lead)
+        e = (bits & ((1 << (sb + 1)) - 1)) - (1 << sb)
+        e_hat = self._to_rns_ntt(e, nlimbs)
+        c0 = ctdata[..., 0, :, :]
+        c1 = ctdata[..., 1, :, :]
+        out = torch.empty_like(c1)
+        for i in range(nlimbs):
+            cs = self.backend.modmul(
+                c1[..., i, :], sk_share[i].expand_as(c1[..., i, :]).contiguous(), i)
+            h = cs + e_hat[..., i, :]
+            if lead:
+                h = h + c0[..., i, :]
+            out[..., i, :] = torch.remainder(h, self._q(i))
+        return out
+
     # ----- homomorphic ops -----
     @staticmethod
     def _check_add_scales(sa: float, sb: float) -> None:
@@ -611,6 +748,30 @@ class CKKSContext:
             return vals.reshape(-1)[:ct.count].to(torch.float32)
         flat = torch.from_numpy(np.ascontiguousarray(vals.reshape(-1)[:ct.count]))
         return flat.to(torch.float32)
+
+    def _decode_tensor(self, pt: torch.Tensor, scale: float,
+                       count: int) -> torch.Tensor:
+        vals = self.decode(Plaintext(pt, scale), self.slots)  # [B, slots]
+        if torch.is_tensor(vals):
+            return vals.reshape(-1)[:count].to(torch.float32)
+        flat = torch.from_numpy(np.ascontiguousarray(vals.reshape(-1)[:count]))
+        return flat.to(torch.float32)
+
+    def partial_decrypt_tensor(self, ct: CtxtTensor, sk_share: torch.Tensor,
+                               smudge_bits: int, lead: bool,
+                               bits: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """This party's decryption share of a CtxtTensor: int64 [B, Lc, n],
+        ready for a lazy int64 SUM across parties."""
+        return self.partial_decrypt_data(ct.data, sk_share, smudge_bits, lead,
+                                         bits=bits)
+
+    def combine_shares_tensor(self, share_sum_lazy: torch.Tensor, scale: float,
+                              count: int) -> torch.Tensor:
+        """Lazy int64 SUM of <= 8 parties' shares [B, Lc, n] -> fp32 vector.
+        Each share is < q < 2^60, so the sum is < 2^63 and the modreduce
+        conditional-subtract chain applies. Reduces the sum in place."""
+        pt = self._modreduce_(share_sum_lazy)
+        return self._decode_tensor(pt, scale, count)
 
     def add_tensor(self, a: CtxtTensor, b: CtxtTensor) -> CtxtTensor:
         assert a.count == b.count and a.level == b.level
@@ -773,3 +934,17 @@ class CKKSContext:
                           device=ct.data.device)
         ct.data.remainder_(qs.view(1, 1, -1, 1))
         return ct
+
+    def _modreduce_(self, data: torch.Tensor) -> torch.Tensor:
+        """In-place modreduce of any lazily-summed [..., L', n] tensor over
+        the first L' chain primes (ciphertexts, b_i sums, decryption shares)."""
+        nlimbs = data.shape[-2]
+        if self.device.type == "cuda":
+            # branchless conditional-subtract kernel (sum of <= 8 residues)
+            self.backend._C.modreduce_(
+                data, self.backend.qs[:nlimbs].contiguous())
+            return data
+        qs = torch.tensor(self.primes[:nlimbs], dtype=torch.int64,
+                          device=data.device)
+        data.remainder_(qs.view(-1, 1))
+        return data
