@@ -118,6 +118,17 @@ std::vector<torch::Tensor> dense_head2_fwd(torch::Tensor x,
 std::vector<torch::Tensor> dense_head2_bwd(torch::Tensor dlogits,
                                            torch::Tensor x, torch::Tensor h1,
                                            torch::Tensor w1, torch::Tensor w2);
+std::vector<torch::Tensor> linear_bwd_pair(torch::Tensor dy, torch::Tensor w,
+                                           torch::Tensor x);
+std::vector<torch::Tensor> head_xent_fwd(torch::Tensor h1, torch::Tensor w2,
+                                         torch::Tensor b2,
+                                         torch::Tensor labels,
+                                         torch::Tensor acc_loss,
+                                         torch::Tensor acc_correct);
+std::vector<torch::Tensor> head_xent_bwd(torch::Tensor probs,
+                                         torch::Tensor labels,
+                                         torch::Tensor dloss, torch::Tensor h1,
+                                         torch::Tensor w2);
 void pack_mt(torch::Tensor meta, torch::Tensor ptrs, torch::Tensor sizes,
              torch::Tensor offs, int64_t nchunks, torch::Tensor flat);
 void unpack_mt(torch::Tensor flat, torch::Tensor meta, torch::Tensor ptrs,
@@ -199,6 +210,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("dense_head2_fwd", &dense_head2_fwd);
     m.def("dense_head2_bwd", &dense_head2_bwd,
           "single-launch backward of the 2-layer dense head (M <= 32)");
+    m.def("linear_bwd_pair", &linear_bwd_pair,
+          "dense backward pair in one launch: (dx = dy.w, dw = dy^T.x)");
+    m.def("head_xent_fwd", &head_xent_fwd,
+          "classifier tail forward: (logits, probs, loss), M<=64 H<=128 C<=16");
+    m.def("head_xent_bwd", &head_xent_bwd,
+          "classifier tail backward: (dW2, db2, dz1, db1)");
     m.def("pack_mt", &pack_mt);
     m.def("unpack_mt", &unpack_mt);
     m.def("adam_prep_epoch", &adam_prep_epoch);

@@ -61,6 +61,10 @@
 //   synth_batch_kernel<AUG>        one-pass synthetic data generation,
 //                                  AUG = in-kernel zoom/shear/flip via
 //                                  inverse-affine template sampling
+//   head_xent_fwd/bwd_kernel       classifier tail (last Dense + softmax-CE
+//                                  and their backward) in two single-
+//                                  workgroup launches
+//   linear_bwd_pair_kernel         dense dgrad + wgrad in one launch
 //   maxpool_gen_fwd/bwd_kernel     generic k/s/p pooling (ResNet stem)
 //   avgpool_global_fwd/bwd_kernel  global average pool
 //   add_relu_kernel                residual add + ReLU (bf16x8)
@@ -134,17 +138,20 @@ __device__ __forceinline__ f32x4 tile_mfma_step(const TileSmem& sm, int wave,
 // OUT_BF16: write bf16, else f32.
 // ---------------------------------------------------------------------------
 
+// The tile body is a __device__ template so the paired dense-backward
+// launch (linear_bwd_pair_kernel) runs the very same code per role as the
+// stand-alone kernels: bx/by are the role's own tile coordinates.
 template <bool AT, bool BT, bool OUT_BF16, bool ACCUM>
-__global__ void __launch_bounds__(TPB)
-gemm_kernel(const unsigned short* __restrict__ A,
-            const unsigned short* __restrict__ B, void* __restrict__ C,
-            const float* __restrict__ bias, int M, int N, int K, int relu) {
-    __shared__ TileSmem sm;
+__device__ __forceinline__ void
+gemm_tile_body(TileSmem& sm, const unsigned short* __restrict__ A,
+               const unsigned short* __restrict__ B, void* __restrict__ C,
+               const float* __restrict__ bias, int M, int N, int K, int relu,
+               int bx, int by) {
     const int tid = threadIdx.x;
     const int wave = tid >> 6;
     const int lane = tid & 63;
-    const int m0 = blockIdx.x * BM;
-    const int n0 = blockIdx.y * BN;
+    const int m0 = bx * BM;
+    const int n0 = by * BN;
 
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int k0 = 0; k0 < K; k0 += BK) {
@@ -195,6 +202,43 @@ gemm_kernel(const unsigned short* __restrict__ A,
         } else {
             reinterpret_cast<float*>(C)[(int64_t)row * N + col] = v;
         }
+    }
+}
+
+template <bool AT, bool BT, bool OUT_BF16, bool ACCUM>
+__global__ void __launch_bounds__(TPB)
+gemm_kernel(const unsigned short* __restrict__ A,
+            const unsigned short* __restrict__ B, void* __restrict__ C,
+            const float* __restrict__ bias, int M, int N, int K, int relu) {
+    __shared__ TileSmem sm;
+    gemm_tile_body<AT, BT, OUT_BF16, ACCUM>(sm, A, B, C, bias, M, N, K, relu,
+                                            blockIdx.x, blockIdx.y);
+}
+
+// Dense backward pair: dx = dy.w (z = 0) and dw = dy^T.x (z = 1) in ONE
+// launch. The two products are independent and both read dy; as separate
+// launches each paid its own dependent kernel boundary. Per-role arithmetic
+// and store order are those of gemm_kernel<false,false,true,false> and
+// gemm_kernel<true,false,false,false>, so outputs are bit-identical. The
+// grid is the larger of the two tile grids; surplus blocks exit at once.
+__global__ void __launch_bounds__(TPB)
+linear_bwd_pair_kernel(const unsigned short* __restrict__ dy,   // [M, N]
+                       const unsigned short* __restrict__ w,    // [N, K]
+                       const unsigned short* __restrict__ x,    // [M, K]
+                       unsigned short* __restrict__ dx,         // [M, K]
+                       float* __restrict__ dw,                  // [N, K]
+                       int M, int N, int K) {
+    __shared__ TileSmem sm;
+    if (blockIdx.z == 0) {
+        if ((int)blockIdx.x * BM >= M) return;
+        gemm_tile_body<false, false, true, false>(sm, dy, w, dx, nullptr, M,
+                                                  K, N, 0, blockIdx.x,
+                                                  blockIdx.y);
+    } else {
+        if ((int)blockIdx.x * BM >= N) return;
+        gemm_tile_body<true, false, false, false>(sm, dy, x, dw, nullptr, N,
+                                                  K, M, 0, blockIdx.x,
+                                                  blockIdx.y);
     }
 }
 
@@ -2367,21 +2411,14 @@ dense_head2_bwd_kernel(const unsigned short* __restrict__ dl_g,  // [M, N2]
 // persistent buffers — replacing a ~7-kernel torch chain per step.
 // SINGLE_BLOCK: grid(1) with an intra-block reduction — loss is written
 // directly (no zero-fill + atomics); rows strided over the block's waves.
-template <bool SINGLE_BLOCK>
-__global__ void softmax_xent_fwd_kernel(const unsigned short* __restrict__ logits,
-                                        const int64_t* __restrict__ labels,
-                                        float* __restrict__ probs,
-                                        float* __restrict__ loss, int M, int C,
-                                        float* __restrict__ acc_loss,
-                                        float* __restrict__ acc_correct) {
-    __shared__ float lred[2][8];
-    const int lane = threadIdx.x & 63;
-    const int nw = blockDim.x / 64;
-    float my_loss = 0.f, my_corr = 0.f;
-    for (int row = SINGLE_BLOCK ? (threadIdx.x >> 6)
-                                : blockIdx.x * nw + (threadIdx.x >> 6);
-         row < M; row += SINGLE_BLOCK ? nw : gridDim.x * nw) {
-    const unsigned short* lr = logits + (int64_t)row * C;
+// Per-row softmax / argmax / loss arithmetic, one wave per row; shared by
+// softmax_xent_fwd_kernel and head_xent_fwd_kernel so both produce the same
+// bits. `lr` is the row's bf16 logits (global or LDS). Writes the row's
+// probs; on lane 0 returns the row's loss term and whether argmax == label.
+__device__ __forceinline__ void softmax_xent_row(
+    const unsigned short* lr, const int64_t* __restrict__ labels, int row,
+    float* __restrict__ probs, int M, int C, int lane, float& l,
+    bool& correct) {
     float mx = -3.4e38f;
     int arg = 0;
     for (int c = lane; c < C; c += 64) {
@@ -2401,42 +2438,82 @@ __global__ void softmax_xent_fwd_kernel(const unsigned short* __restrict__ logit
     float inv = 1.f / sum;
     for (int c = lane; c < C; c += 64)
         probs[(int64_t)row * C + c] = __expf(bf2f(lr[c]) - mx) * inv;
+    l = 0.f;
+    correct = false;
     if (lane == 0) {
         int64_t lab = labels[row];
         float p = __expf(bf2f(lr[lab]) - mx) * inv;
-        float l = -__logf(fmaxf(p, 1e-30f)) / M;
-        if (SINGLE_BLOCK) {
-            my_loss += l;
-            if (arg == (int)lab) my_corr += 1.f;
-        } else {
-            atomicAdd(loss, l);
-            if (acc_loss) atomicAdd(acc_loss, l);
-            if (acc_correct && arg == (int)lab) atomicAdd(acc_correct, 1.f);
-        }
+        l = -__logf(fmaxf(p, 1e-30f)) / M;
+        correct = arg == (int)lab;
     }
-    }  // row loop
-    if (SINGLE_BLOCK) {
-        const int w = threadIdx.x >> 6;
+}
+
+// Single-block epilogue: per-wave partials -> loss written directly (no
+// zero-fill), stats accumulated into the persistent buffers.
+__device__ __forceinline__ void softmax_xent_block_finish(
+    float (*lred)[8], float my_loss, float my_corr, float* __restrict__ loss,
+    float* __restrict__ acc_loss, float* __restrict__ acc_correct) {
+    const int lane = threadIdx.x & 63;
+    const int nw = blockDim.x / 64;
+    const int w = threadIdx.x >> 6;
+    if (lane == 0) {
+        lred[0][w] = my_loss;
+        lred[1][w] = my_corr;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float L = 0.f, Cc = 0.f;
+        for (int i = 0; i < nw; ++i) {
+            L += lred[0][i];
+            Cc += lred[1][i];
+        }
+        loss[0] = L;                      // direct write: no zero-fill
+        if (acc_loss) atomicAdd(acc_loss, L);
+        if (acc_correct) atomicAdd(acc_correct, Cc);
+    }
+}
+
+template <bool SINGLE_BLOCK>
+__global__ void softmax_xent_fwd_kernel(const unsigned short* __restrict__ logits,
+                                        const int64_t* __restrict__ labels,
+                                        float* __restrict__ probs,
+                                        float* __restrict__ loss, int M, int C,
+                                        float* __restrict__ acc_loss,
+                                        float* __restrict__ acc_correct) {
+    __shared__ float lred[2][8];
+    const int lane = threadIdx.x & 63;
+    const int nw = blockDim.x / 64;
+    float my_loss = 0.f, my_corr = 0.f;
+    for (int row = SINGLE_BLOCK ? (threadIdx.x >> 6)
+                                : blockIdx.x * nw + (threadIdx.x >> 6);
+         row < M; row += SINGLE_BLOCK ? nw : gridDim.x * nw) {
+        float l;
+        bool correct;
+        softmax_xent_row(logits + (int64_t)row * C, labels, row, probs, M, C,
+                         lane, l, correct);
         if (lane == 0) {
-            lred[0][w] = my_loss;
-            lred[1][w] = my_corr;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float L = 0.f, Cc = 0.f;
-            for (int i = 0; i < nw; ++i) {
-                L += lred[0][i];
-                Cc += lred[1][i];
+            if (SINGLE_BLOCK) {
+                my_loss += l;
+                if (correct) my_corr += 1.f;
+            } else {
+                atomicAdd(loss, l);
+                if (acc_loss) atomicAdd(acc_loss, l);
+                if (acc_correct && correct) atomicAdd(acc_correct, 1.f);
             }
-            loss[0] = L;                      // direct write: no zero-fill
-            if (acc_loss) atomicAdd(acc_loss, L);
-            if (acc_correct) atomicAdd(acc_correct, Cc);
         }
     }
+    if (SINGLE_BLOCK)
+        softmax_xent_block_finish(lred, my_loss, my_corr, loss, acc_loss,
+                                  acc_correct);
 }
 
 // dloss is a device scalar (graph-capture safe: no host readback of the
 // upstream gradient); scale = dloss / M.
+__device__ __forceinline__ float xent_dlogit(float p, bool is_label,
+                                             float scale) {
+    return (p - (is_label ? 1.f : 0.f)) * scale;
+}
+
 template <bool OUT_BF16>
 __global__ void softmax_xent_bwd_kernel(const float* __restrict__ probs,
                                         const int64_t* __restrict__ labels,
@@ -2449,12 +2526,241 @@ __global__ void softmax_xent_bwd_kernel(const float* __restrict__ probs,
          i += (int64_t)gridDim.x * blockDim.x) {
         int64_t row = i / C;
         int c = i % C;
-        float g = (probs[i] - (labels[row] == c ? 1.f : 0.f)) * scale;
+        float g = xent_dlogit(probs[i], labels[row] == c, scale);
         if (OUT_BF16)
             reinterpret_cast<unsigned short*>(dlogits)[i] = f2bf(g);
         else
             reinterpret_cast<float*>(dlogits)[i] = g;
     }
+}
+
+// ---------------------------------------------------------------------------
+// Classifier tail: the last Dense(relu, bias) -> Dense(bias) -> softmax-CE
+// (mean) as TWO single-workgroup launches. h1 is the post-ReLU output of the
+// penultimate layer [M, H]; w2 is the last layer's weight [C, H].
+//
+//   head_xent_fwd_kernel   logits = bf16(h1.w2^T + b2), probs, loss, stats
+//   head_xent_bwd_kernel   dlogits -> dW2, db2, dz1 (relu-gated dh1), db1
+//
+// They replace seven launches (fc2 fwd, softmax fwd/bwd, bias grad, fc2
+// dgrad/wgrad, relu+bias bwd) that each ran at the dependent-launch floor on
+// a working set (<= 64x128 activations, <= 16x128 weight) that fits one
+// workgroup's LDS. Every 800-wide GEMM stays on its multi-block kernel.
+//
+// Rounding points are those of the composed path: the three products use the
+// same MFMA k-order and zero padding as linear_splitk_kernel / gemm_kernel
+// (k chunks of 32, accumulated in order), logits are rounded to bf16 before
+// the softmax, dlogits = bf16((p - onehot) * dloss / M), dh1 is rounded to
+// bf16 before the gate, and the f32 column sums db1 / db2 follow the
+// summation order of relu_bias_bwd_kernel / bias_grad_kernel: every output
+// is bit-identical to the composed launches.
+//
+// Envelope (host-checked): M <= 64, H <= 128, C <= 16, any H and C inside.
+// LDS images are zero-padded to the MFMA tile so every k-slot is defined.
+// ---------------------------------------------------------------------------
+
+constexpr int HX_MP = 64;          // padded batch rows
+constexpr int HX_HP = 128;         // padded hidden width
+constexpr int HX_LD = HX_HP + 8;   // LDS row stride (16-B pad)
+constexpr int HX_CP = 32;          // padded classes (one MFMA k-step)
+constexpr int HX_TPB = 512;        // 8 waves, as softmax_xent_fwd_kernel<true>
+
+// Stage src[rows, cols] (bf16, row-major, contiguous) into a zero-padded LDS
+// image dst[prow][HX_LD]: 16-B global loads wherever the 8-element chunk is
+// 16-B aligned in memory and inside the row, element loads otherwise (odd
+// rows when cols % 8 != 0); always 16-B LDS stores.
+__device__ __forceinline__ void hx_stage(unsigned short (*dst)[HX_LD],
+                                         int prow,
+                                         const unsigned short* __restrict__ src,
+                                         int rows, int cols) {
+    const bool base16 = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+    for (int i = threadIdx.x; i < prow * (HX_HP / 8); i += blockDim.x) {
+        const int r = i / (HX_HP / 8);
+        const int c8 = (i % (HX_HP / 8)) * 8;
+        u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (r < rows && c8 < cols) {
+            const int g = r * cols + c8;
+            if (base16 && c8 + 8 <= cols && (g & 7) == 0) {
+                v = *reinterpret_cast<const u16x8*>(src + g);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (c8 + j < cols) v[j] = src[g + j];
+            }
+        }
+        *reinterpret_cast<u16x8*>(&dst[r][c8]) = v;
+    }
+}
+
+__global__ void __launch_bounds__(HX_TPB)
+head_xent_fwd_kernel(const unsigned short* __restrict__ h1,   // [M, H]
+                     const unsigned short* __restrict__ w2,   // [C, H]
+                     const float* __restrict__ b2,            // [C]
+                     const int64_t* __restrict__ labels,      // [M]
+                     unsigned short* __restrict__ logits,     // [M, C]
+                     float* __restrict__ probs,               // [M, C]
+                     float* __restrict__ loss, int M, int H, int C,
+                     float* __restrict__ acc_loss,
+                     float* __restrict__ acc_correct) {
+    __shared__ unsigned short h1s[HX_MP][HX_LD];
+    __shared__ unsigned short w2s[16][HX_LD];
+    __shared__ unsigned short lg[HX_MP][16];     // bf16 logits
+    __shared__ float lred[2][8];
+    const int tid = threadIdx.x;
+    const int wave = tid >> 6;
+    const int lane = tid & 63;
+    const int half = lane >> 4, sub = lane & 15;
+    hx_stage(h1s, HX_MP, h1, M, H);
+    hx_stage(w2s, 16, w2, C, H);
+    __syncthreads();
+    // logits: one 16-row tile per wave, k over H in steps of 32 (the
+    // linear_splitk_kernel<1> order), bias added after the accumulation
+    if (wave * 16 < M) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < H; k += 32) {
+            bf16x8 a = *reinterpret_cast<const bf16x8*>(
+                &h1s[wave * 16 + sub][k + half * 8]);
+            bf16x8 b = *reinterpret_cast<const bf16x8*>(
+                &w2s[sub][k + half * 8]);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+        }
+        const float bv = sub < C ? b2[sub] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = wave * 16 + half * 4 + r;
+            const unsigned short q = f2bf(acc[r] + bv);
+            lg[row][sub] = q;
+            if (row < M && sub < C) logits[row * C + sub] = q;
+        }
+    }
+    __syncthreads();
+    float my_loss = 0.f, my_corr = 0.f;
+    for (int row = wave; row < M; row += HX_TPB / 64) {
+        float l;
+        bool correct;
+        softmax_xent_row(lg[row], labels, row, probs, M, C, lane, l, correct);
+        if (lane == 0) {
+            my_loss += l;
+            if (correct) my_corr += 1.f;
+        }
+    }
+    softmax_xent_block_finish(lred, my_loss, my_corr, loss, acc_loss,
+                              acc_correct);
+}
+
+__global__ void __launch_bounds__(HX_TPB)
+head_xent_bwd_kernel(const float* __restrict__ probs,         // [M, C]
+                     const int64_t* __restrict__ labels,      // [M]
+                     const float* __restrict__ dloss,         // scalar
+                     const unsigned short* __restrict__ h1,   // [M, H]
+                     const unsigned short* __restrict__ w2,   // [C, H]
+                     float* __restrict__ dw2,                 // [C, H]
+                     float* __restrict__ db2,                 // [C]
+                     unsigned short* __restrict__ dz1,        // [M, H]
+                     float* __restrict__ db1,                 // [H]
+                     int M, int H, int C) {
+    __shared__ unsigned short h1s[HX_MP][HX_LD];   // post-relu activations
+    __shared__ unsigned short dzs[HX_MP][HX_LD];   // gated dh1
+    __shared__ unsigned short w2s[HX_CP][HX_LD];   // w2, zero-padded rows
+    __shared__ unsigned short dl[HX_MP][HX_CP];    // dlogits, zero-padded
+    const int tid = threadIdx.x;
+    const int wave = tid >> 6;
+    const int lane = tid & 63;
+    const int half = lane >> 4, sub = lane & 15;
+    // ---- stage (every pad slot written: all MFMA k-slots are defined) ----
+    const float scale = dloss[0] / (float)M;
+    for (int i = tid; i < HX_MP * HX_CP; i += HX_TPB) {
+        const int m = i / HX_CP, c = i % HX_CP;
+        unsigned short q = 0;
+        if (m < M && c < C)
+            q = f2bf(xent_dlogit(probs[m * C + c], labels[m] == c, scale));
+        dl[m][c] = q;
+    }
+    hx_stage(h1s, HX_MP, h1, M, H);
+    hx_stage(w2s, HX_CP, w2, C, H);
+    __syncthreads();
+    // ---- wave-strided tile list: dW2 tiles, then dh1 tiles ----
+    const int h16 = (H + 15) / 16;
+    const int m16 = (M + 15) / 16;
+    const int total = h16 + m16 * h16;
+    for (int t = wave; t < total; t += HX_TPB / 64) {
+        bf16x8 a, b;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        if (t < h16) {
+            // dW2[c, h] = sum_m dl[m][c] * h1[m][h], k = m in steps of 32
+            // (gemm_kernel<true,false,false,false> order)
+            const int cb = t * 16;
+            for (int kk = 0; kk < M; kk += 32) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    a[j] = *reinterpret_cast<const bf16_t*>(
+                        &dl[kk + half * 8 + j][sub]);
+                    b[j] = *reinterpret_cast<const bf16_t*>(
+                        &h1s[kk + half * 8 + j][cb + sub]);
+                }
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc,
+                                                              0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int c = half * 4 + r, h = cb + sub;
+                if (c < C && h < H) dw2[c * H + h] = acc[r];
+            }
+        } else {
+            // dh1[m, h] = sum_c dl[m][c] * w2[c][h]: one k-step (C <= 16,
+            // zero-padded to 32), rounded to bf16, then gated on h1 > 0
+            const int tt = t - h16;
+            const int rb = (tt / h16) * 16;
+            const int cb = (tt % h16) * 16;
+            a = *reinterpret_cast<const bf16x8*>(&dl[rb + sub][half * 8]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                b[j] = *reinterpret_cast<const bf16_t*>(
+                    &w2s[half * 8 + j][cb + sub]);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int m = rb + half * 4 + r, h = cb + sub;
+                const unsigned short hv = h1s[m][h];
+                const bool act = (hv & 0x7fffu) != 0 && !(hv & 0x8000u);
+                const unsigned short q = act ? f2bf(acc[r]) : (unsigned short)0;
+                dzs[m][h] = q;
+                if (m < M && h < H) dz1[m * H + h] = q;
+            }
+        }
+    }
+    __syncthreads();
+    // ---- bias grads, lane-parallel and in the summation ORDER of the
+    // kernels they replace, so both are bit-identical to the composed path:
+    //  db2 (waves 4-7, a wave per class column): bias_grad_kernel's order,
+    //      one row per lane, then a pairwise tree (off = 32 .. 1);
+    //  db1 (threads 0-255): relu_bias_bwd_kernel's order, thread =
+    //      (column, row-lane), row-strided partial sums, LDS tree.
+    float* red = reinterpret_cast<float*>(&w2s[0][0]);   // w2s is dead: reuse
+    int rlanes = 256 / H;
+    rlanes = 1 << (31 - __clz(rlanes));
+    const int c1 = tid % H, rl = tid / H;
+    if (tid < 256) {
+        float acc = 0.f;
+        if (rl < rlanes)
+            for (int m = rl; m < M; m += rlanes) acc += bf2f(dzs[m][c1]);
+        red[tid] = acc;
+    } else {
+        for (int c = wave - 4; c < C; c += 4) {
+            float v = 0.f;
+            if (lane < M) v += bf2f(dl[lane][c]);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1)
+                v += __shfl_down(v, off, 64);
+            if (lane == 0) db2[c] = v;
+        }
+    }
+    __syncthreads();
+    for (int off = rlanes >> 1; off >= 1; off >>= 1) {
+        if (tid < 256 && rl < off) red[tid] += red[tid + off * H];
+        __syncthreads();
+    }
+    if (tid < 256 && rl == 0) db1[c1] = red[tid];
 }
 
 // ---------------------------------------------------------------------------
@@ -4136,6 +4442,88 @@ torch::Tensor linear_wgrad(torch::Tensor dy, torch::Tensor x) {
                        0, at::cuda::getCurrentCUDAStream(), bf_ptr(dy), bf_ptr(x),
                        dw.data_ptr<float>(), nullptr, N, K, M, 0);
     return dw;
+}
+
+std::vector<torch::Tensor> linear_bwd_pair(torch::Tensor dy, torch::Tensor w,
+                                           torch::Tensor x) {
+    CHECK_GPU(dy);
+    TORCH_CHECK(dy.is_contiguous() && w.is_contiguous() && x.is_contiguous());
+    const int M = (int)dy.size(0), N = (int)dy.size(1), K = (int)w.size(1);
+    TORCH_CHECK(w.size(0) == N && x.size(0) == M && x.size(1) == K,
+                "linear_bwd_pair shape mismatch");
+    auto dx = torch::empty({M, K}, dy.options());
+    auto dw = torch::empty({N, K}, dy.options().dtype(torch::kFloat32));
+    // z = 0: dx tiles (ceil(M/BM) x ceil(K/BN)); z = 1: dw tiles
+    // (ceil(N/BM) x ceil(K/BN)); same y extent, x is the larger of the two
+    dim3 grid(std::max(ceildiv(M, BM), ceildiv(N, BM)), ceildiv(K, BN), 2);
+    hipLaunchKernelGGL(linear_bwd_pair_kernel, grid, dim3(TPB), 0,
+                       at::cuda::getCurrentCUDAStream(), bf_ptr(dy), bf_ptr(w),
+                       bf_ptr(x), bf_ptr_mut(dx), dw.data_ptr<float>(), M, N,
+                       K);
+    return {dx, dw};
+}
+
+static void head_xent_check(const torch::Tensor& h1, const torch::Tensor& w2,
+                            int64_t M, int64_t H, int64_t C) {
+    TORCH_CHECK(h1.is_contiguous() && w2.is_contiguous());
+    TORCH_CHECK(h1.scalar_type() == torch::kBFloat16 &&
+                w2.scalar_type() == torch::kBFloat16,
+                "head_xent expects bf16 h1 / w2");
+    TORCH_CHECK(M >= 1 && M <= HX_MP && H >= 1 && H <= HX_HP && C >= 1 &&
+                C <= 16 && w2.size(1) == H,
+                "head_xent shape envelope: M <= 64, H <= 128, C <= 16");
+}
+
+// Returns {logits bf16 [M,C], probs f32 [M,C], loss f32 scalar}.
+std::vector<torch::Tensor> head_xent_fwd(torch::Tensor h1, torch::Tensor w2,
+                                         torch::Tensor b2,
+                                         torch::Tensor labels,
+                                         torch::Tensor acc_loss,
+                                         torch::Tensor acc_correct) {
+    CHECK_GPU(h1);
+    const int M = (int)h1.size(0), H = (int)h1.size(1), C = (int)w2.size(0);
+    head_xent_check(h1, w2, M, H, C);
+    TORCH_CHECK(b2.numel() == C && labels.numel() == M);
+    auto f32 = h1.options().dtype(torch::kFloat32);
+    auto logits = torch::empty({M, C}, h1.options());
+    auto probs = torch::empty({M, C}, f32);
+    auto loss = torch::empty({}, f32);
+    hipLaunchKernelGGL(head_xent_fwd_kernel, dim3(1), dim3(HX_TPB), 0,
+                       at::cuda::getCurrentCUDAStream(), bf_ptr(h1),
+                       bf_ptr(w2), b2.data_ptr<float>(),
+                       labels.data_ptr<int64_t>(), bf_ptr_mut(logits),
+                       probs.data_ptr<float>(), loss.data_ptr<float>(), M, H,
+                       C,
+                       acc_loss.numel() ? acc_loss.data_ptr<float>() : nullptr,
+                       acc_correct.numel() ? acc_correct.data_ptr<float>()
+                                           : nullptr);
+    return {logits, probs, loss};
+}
+
+// Returns {dW2 f32 [C,H], db2 f32 [C], dz1 bf16 [M,H], db1 f32 [H]}; each
+// its own allocation, fully written by the kernel (autograd steals them).
+std::vector<torch::Tensor> head_xent_bwd(torch::Tensor probs,
+                                         torch::Tensor labels,
+                                         torch::Tensor dloss, torch::Tensor h1,
+                                         torch::Tensor w2) {
+    CHECK_GPU(probs);
+    const int M = (int)h1.size(0), H = (int)h1.size(1), C = (int)w2.size(0);
+    head_xent_check(h1, w2, M, H, C);
+    TORCH_CHECK(probs.is_contiguous() && probs.size(0) == M &&
+                probs.size(1) == C && labels.numel() == M &&
+                dloss.numel() == 1);
+    auto f32 = h1.options().dtype(torch::kFloat32);
+    auto dw2 = torch::empty({C, H}, f32);
+    auto db2 = torch::empty({C}, f32);
+    auto dz1 = torch::empty({M, H}, h1.options());
+    auto db1 = torch::empty({H}, f32);
+    hipLaunchKernelGGL(head_xent_bwd_kernel, dim3(1), dim3(HX_TPB), 0,
+                       at::cuda::getCurrentCUDAStream(),
+                       probs.data_ptr<float>(), labels.data_ptr<int64_t>(),
+                       dloss.data_ptr<float>(), bf_ptr(h1), bf_ptr(w2),
+                       dw2.data_ptr<float>(), db2.data_ptr<float>(),
+                       bf_ptr_mut(dz1), db1.data_ptr<float>(), M, H, C);
+    return {dw2, db2, dz1, db1};
 }
 
 static torch::Tensor synth_launch(torch::Tensor templates,

@@ -82,10 +82,19 @@ class LocalClient:
             return self._graphed_step(x, y)
         return self._eager_step(x, y)
 
+    def _loss_logits(self, x, y, acc_loss=None, acc_correct=None):
+        """(loss, logits): models with a fusable classifier tail expose
+        forward_loss (one launch for last Dense + softmax-CE); the others
+        (ResNet) run forward then the loss."""
+        fl = getattr(self.model, "forward_loss", None)
+        if fl is not None:
+            return fl(x, y, acc_loss, acc_correct)
+        logits = self.model(x)
+        return softmax_xent(logits, y, acc_loss, acc_correct), logits
+
     def _eager_step(self, x: torch.Tensor, y: torch.Tensor):
         x = x.to(self.compute_dtype)
-        logits = self.model(x)
-        loss = softmax_xent(logits, y)
+        loss, logits = self._loss_logits(x, y)
         self.opt.zero_grad_() if self.use_graphs else self.opt.zero_grad()
         loss.backward()
         self.opt.step()
@@ -137,9 +146,10 @@ class LocalClient:
         # from the graph pool; replays rewrite them in place
         self.opt.zero_grad()
         with torch.cuda.graph(g, stream=side):
-            logits = self.model(sx.to(self.compute_dtype))
             # stats accumulate INSIDE the loss kernel into persistent buffers
-            loss = softmax_xent(logits, sy, self._acc_loss, self._acc_correct)
+            loss, logits = self._loss_logits(sx.to(self.compute_dtype), sy,
+                                             self._acc_loss,
+                                             self._acc_correct)
             # persistent gradient seed: no per-step ones() fill kernel
             loss.backward(gradient=self._one)
         mt = self.opt.build_mt_table()  # this graph's stolen-grad pointers
@@ -152,8 +162,7 @@ class LocalClient:
 
     def _eager_warmup(self, x, y, clear_grads=False):
         self.opt.zero_grad()  # grads=None: fresh tensors each warmup step
-        logits = self.model(x.to(self.compute_dtype))
-        loss = softmax_xent(logits, y)
+        loss, logits = self._loss_logits(x.to(self.compute_dtype), y)
         loss.backward()
         self.opt.step()
         if clear_grads:
@@ -260,9 +269,9 @@ class LocalClient:
                 self.opt.prep_epoch(steps)
                 for s, i in enumerate(range(0, n, B)):
                     self.opt.zero_grad()  # grads=None -> backward steals
-                    logits = self.model(X[i:i + B])
-                    loss = softmax_xent(logits, Y[i:i + B], self._acc_loss,
-                                        self._acc_correct)
+                    loss, logits = self._loss_logits(
+                        X[i:i + B], Y[i:i + B], self._acc_loss,
+                        self._acc_correct)
                     loss.backward(gradient=self._one)
                     rows_per_step.append(self.opt.current_ptr_rows())
                     self.opt.step_mt_at(shells[s], s, zero_grad=no_zero)
@@ -434,8 +443,8 @@ class LocalClient:
         acc_sum = torch.zeros((), dtype=torch.float32, device=dev)
         steps = samples = 0
         for x, y in loader:
-            logits = self.model(x.to(self.compute_dtype))
-            loss_sum += softmax_xent(logits, y).detach().float()
+            loss, logits = self._loss_logits(x.to(self.compute_dtype), y)
+            loss_sum += loss.detach().float()
             acc_sum += (logits.detach().float().argmax(-1) == y).float().sum()
             steps += 1
             samples += y.numel()

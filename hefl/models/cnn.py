@@ -92,6 +92,28 @@ class _SeqCNN(nn.Module):
             x = m(x)
         return x
 
+    def forward_loss(self, x, labels, acc_loss=None, acc_correct=None):
+        """(loss, logits) with the classifier tail fused where the head
+        qualifies: trunk and any leading Dense layers as in forward(), then
+        Fx.dense_head2_xent on the last Dense(relu, bias) -> Dense(bias)
+        and the loss. Otherwise softmax_xent(self(x), ...)."""
+        from ..ops import functional as Fx
+        h = self.head
+        ok = (len(h) >= 2 and h[-2].relu and not h[-1].relu
+              and h[-2].bias is not None and h[-1].bias is not None
+              and not self._head2_ok and not self._head2f_ok)
+        if not ok:
+            logits = self(x)
+            return Fx.softmax_xent(logits, labels, acc_loss,
+                                   acc_correct), logits
+        for m in self.trunk:
+            x = m(x)
+        x = self.flatten(x)
+        for m in h[:-2]:
+            x = m(x)
+        return Fx.dense_head2_xent(x, h[-2].weight, h[-2].bias, h[-1].weight,
+                                   h[-1].bias, labels, acc_loss, acc_correct)
+
     def n_params(self) -> int:
         return sum(p.numel() for p in self.parameters())
 

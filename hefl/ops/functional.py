@@ -72,6 +72,16 @@ def _fork_side(dev):
         _SIDE_STREAMS[dev] = s
     return s
 
+# Classifier-tail fusion (default ON, HEFL_HEAD_XENT=0 restores the
+# composed tail): dense_head2_xent runs the last Dense(relu) -> Dense ->
+# softmax-CE as head_xent_fwd + head_xent_bwd, two single-workgroup launches
+# in place of seven launches at the dependent-launch floor.
+_HEAD_XENT = os.getenv("HEFL_HEAD_XENT", "1") != "0"
+# Paired dense backward (default ON, HEFL_LIN_PAIR=0 restores the separate
+# launches): dgrad and wgrad of a Dense layer in ONE launch (blockIdx.z
+# selects the role; bit-identical outputs).
+_LIN_PAIR = os.getenv("HEFL_LIN_PAIR", "1") != "0"
+
 # Epoch-graph capture contract (fl/client.py sets this around warmup +
 # capture; HEFL_GRAPH_NO_ZERO=0 disables): while True, conv dw / bias db
 # outputs skip their zero-init fill launch — the gkey passed to the C++
@@ -343,8 +353,13 @@ class _LinearFn(torch.autograd.Function):
                 dy = _C().relu_bwd(dy, y)
             elif ctx.has_bias:
                 db = _C().bias_grad(dy.view(-1, dy.shape[-1]), gkey=bkey)
-            dx = _C().linear_dgrad(dy, w) if ctx.needs_input_grad[0] else None
-            dw = _C().linear_wgrad(dy, x).to(torch.float32)
+            if ctx.needs_input_grad[0] and _LIN_PAIR:
+                dx, dw = _C().linear_bwd_pair(dy, w.contiguous(),
+                                              x.contiguous())
+            else:
+                dx = _C().linear_dgrad(dy, w) \
+                    if ctx.needs_input_grad[0] else None
+                dw = _C().linear_wgrad(dy, x).to(torch.float32)
         else:
             dy = dy.float()
             if ctx.relu:
@@ -472,6 +487,71 @@ def softmax_xent(logits, labels, acc_loss=None, acc_correct=None):
     """Fused softmax + CE; on GPU optionally accumulates mean-loss and
     correct-count into persistent device buffers (stats fused in-kernel)."""
     return _SoftmaxXentFn.apply(logits, labels, acc_loss, acc_correct)
+
+
+class _DenseHead2XentFn(torch.autograd.Function):
+    """Dense(relu) -> Dense(logits) -> softmax-CE(mean) with the classifier
+    tail fused (GPU only): fc1 forward is the standard linear_fwd (h1
+    bit-identical to the composed path), then head_xent_fwd produces logits,
+    probs and the loss in one single-workgroup launch; backward is
+    head_xent_bwd (dW2, db2, relu-gated dz1, db1) followed by the fc1
+    dgrad/wgrad pair. Rounding points are those of the composed ops."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, labels, acc_loss, acc_correct):
+        w1b, w2b = _gpu_dtype(w1).contiguous(), _gpu_dtype(w2).contiguous()
+        xc = x.contiguous()
+        empty = torch.empty(0, device=x.device)
+        h1 = _C().linear_fwd(xc, w1b, b1.detach().float(), True)
+        logits, probs, loss = _C().head_xent_fwd(
+            h1, w2b, b2.detach().float(), labels,
+            acc_loss if acc_loss is not None else empty,
+            acc_correct if acc_correct is not None else empty)
+        ctx.save_for_backward(xc, h1, w1b, w2b, probs, labels)
+        ctx.mark_non_differentiable(logits)
+        # logits never receives a gradient: without this autograd would
+        # materialize a zero [M, C] tensor for it (one fill launch per step)
+        ctx.set_materialize_grads(False)
+        return loss, logits
+
+    @staticmethod
+    def backward(ctx, dloss, _dlogits):
+        if dloss is None:
+            return (None,) * 8
+        x, h1, w1b, w2b, probs, labels = ctx.saved_tensors
+        # dloss stays a device scalar (no host sync: hipGraph-capturable)
+        dl = dloss if torch.is_tensor(dloss) else torch.tensor(
+            float(dloss), device=probs.device)
+        dw2, db2, dz1, db1 = _C().head_xent_bwd(
+            probs, labels, dl.to(probs.device, torch.float32), h1, w2b)
+        if not ctx.needs_input_grad[0]:
+            dx, dw1 = None, _C().linear_wgrad(dz1, x)
+        elif _LIN_PAIR:
+            dx, dw1 = _C().linear_bwd_pair(dz1, w1b, x)
+        else:
+            dx = _C().linear_dgrad(dz1, w1b)
+            dw1 = _C().linear_wgrad(dz1, x)
+        return dx, dw1, db1, dw2, db2, None, None, None
+
+
+def head_xent_ok(x, w1, w2) -> bool:
+    """Shape/dtype envelope of the fused classifier tail (cnn.hip head_xent):
+    bf16 activations on GPU, M <= 64, H <= 128, C <= 16."""
+    return (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2
+            and 1 <= x.shape[0] <= 64 and w1.shape[0] <= 128
+            and w2.shape[0] <= 16)
+
+
+def dense_head2_xent(x, w1, b1, w2, b2, labels, acc_loss=None,
+                     acc_correct=None):
+    """loss, logits of Dense(relu, bias) -> Dense(bias) -> softmax-CE(mean).
+    GPU inside the envelope: fused tail; otherwise (and on CPU) literally the
+    composed linear -> linear -> softmax_xent ops."""
+    if _HEAD_XENT and head_xent_ok(x, w1, w2):
+        return _DenseHead2XentFn.apply(x, w1, b1, w2, b2, labels, acc_loss,
+                                       acc_correct)
+    logits = linear(linear(x, w1, b1, relu=True), w2, b2, relu=False)
+    return softmax_xent(logits, labels, acc_loss, acc_correct), logits
 
 
 # ---------------------------------------------------------------------------
