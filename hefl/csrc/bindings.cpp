@@ -44,6 +44,11 @@ torch::Tensor uniform_center_rns(torch::Tensor bits, int64_t smudge_bits,
 torch::Tensor pdec_share(torch::Tensor ct, torch::Tensor s_hat,
                          torch::Tensor e_hat, bool add_c0, torch::Tensor qs,
                          torch::Tensor ratios);
+torch::Tensor galois_lift(torch::Tensor c, int64_t ginv, torch::Tensor qs,
+                          torch::Tensor ratios);
+torch::Tensor galois_perm_add(torch::Tensor ct, torch::Tensor ks0,
+                              torch::Tensor ks1, torch::Tensor perm,
+                              torch::Tensor qs);
 
 // fft.hip
 torch::Tensor fft_encode(torch::Tensor vals, torch::Tensor tw_enc,
@@ -164,6 +169,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "64-bit draws [.., n] -> smudging noise residues [.., L, n]");
     m.def("pdec_share", &pdec_share,
           "threshold decryption share c1*s + e (+ c0) over [.., 2, L, n]");
+    m.def("galois_lift", &galois_lift,
+          "X -> X^g on key-switch digits [.., D, n], lifted to [.., D, Lp, n]");
+    m.def("galois_perm_add", &galois_perm_add,
+          "rotated ciphertext (c0[perm] + ks0, ks1) over [.., 2, L, n]");
     m.def("fft_encode", &fft_encode,
           "CKKS special-FFT encode: f64 slots -> int64 coeffs");
     m.def("fft_decode", &fft_decode,

@@ -28,6 +28,10 @@
 //                                            all-reduce), branchless
 //   cbd21_kernel                             centered-binomial noise from
 //                                            one 64-bit draw (popcounts)
+//   uniform_center_rns / pdec_share kernels  threshold decryption
+//   galois_lift / galois_perm_add kernels    slot rotation: automorphism
+//                                            fused into the digit lift and
+//                                            into the final add
 //
 // Structure per row of length n (n = 2^6 .. 2^15):
 //  * stages whose butterfly span exceeds NBLK run in a strided global-memory
@@ -918,6 +922,97 @@ __global__ void pdec_share_kernel(const int64_t* __restrict__ ct,
     }
 }
 
+// ---------------------------------------------------------------------------
+// Slot rotation / conjugation kernels (CKKSContext.rotate, ckks.py). Both use
+// the gather form: V consecutive OUTPUT coefficients per thread, one 16-byte
+// store per operand at V = 2, sources fetched one by one (an automorphism
+// scatters neighbours). n is a power of two, so every index is masked into
+// [0, n) and cannot leave its row whatever the tables hold.
+// ---------------------------------------------------------------------------
+
+// Coefficient-domain automorphism X -> X^g fused into the key-switch digit
+// broadcast. c is [R, D, n]: digit d holds residues in [0, q_d). Output
+// coefficient k of sigma_g(c) comes from e = k * g^-1 mod 2n: source e mod n,
+// negated when e >= n. The digit is the representative in [0, q_d) (c, or
+// q_d - c for a negated non-zero c), Barrett-reduced into each of the Lp
+// target primes: out [R, D, Lp, n]. qs / ratios are the gathered tables of
+// the Lp limbs (the first D of them are the digits' own primes). One launch
+// replaces a gather, a where and a bcast_center_mod launch.
+template <int V>
+__global__ void galois_lift_kernel(const int64_t* __restrict__ c,
+                                   int64_t* __restrict__ out,
+                                   int64_t total_vec, int64_t n, int D, int Lp,
+                                   int64_t ginv,
+                                   const int64_t* __restrict__ qs,
+                                   const int64_t* __restrict__ ratios) {
+    using Vec = I64Vec<V>;
+    const int64_t mask2n = 2 * n - 1;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+         t < total_vec; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = t * V;              // index into c's [R, D, n] space
+        const int64_t k0 = o % n;
+        const int64_t rd = o / n;             // row * D + d
+        const int d = (int)(rd % D);
+        const uint64_t qd = (uint64_t)qs[d];
+        uint64_t v[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int64_t e = ((k0 + k) * ginv) & mask2n;
+            const uint64_t x = (uint64_t)c[rd * n + (e & (n - 1))];
+            v[k] = (e >= n && x) ? qd - x : x;
+        }
+        int64_t* dst = out + rd * Lp * n + k0;
+        for (int i = 0; i < Lp; ++i) {
+            const uint64_t q = (uint64_t)qs[i];
+            const uint64_t r0 = (uint64_t)ratios[2 * i];
+            const uint64_t r1 = (uint64_t)ratios[2 * i + 1];
+            Vec y;
+#pragma unroll
+            for (int k = 0; k < V; ++k)
+                y.v[k] = (int64_t)barrett_red128(v[k], 0, q, r0, r1);
+            *reinterpret_cast<Vec*>(dst + (int64_t)i * n) = y;
+        }
+    }
+}
+
+// NTT-domain automorphism of c0 (a pure permutation there) fused into the
+// final add and the ciphertext assembly. ct is [R, 2, L, n], c0 read in
+// place; ks0 / ks1 are the key-switch outputs [R, L, n]:
+//   out[r, 0, i, k] = ct[r, 0, i, perm[k]] + ks0[r, i, k]  mod q_i
+//   out[r, 1, i, k] = ks1[r, i, k]
+// One launch replaces an index_select, a modadd_limbs and a torch.stack.
+template <int V>
+__global__ void galois_perm_add_kernel(const int64_t* __restrict__ ct,
+                                       const int64_t* __restrict__ ks0,
+                                       const int64_t* __restrict__ ks1,
+                                       const int32_t* __restrict__ perm,
+                                       int64_t* __restrict__ out,
+                                       int64_t total_vec, int64_t n, int L,
+                                       const int64_t* __restrict__ qs) {
+    using Vec = I64Vec<V>;
+    const int64_t Ln = (int64_t)L * n;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+         t < total_vec; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = t * V;              // index into ks0's [R, L, n] space
+        const int64_t k0 = o % n;
+        const int l = (int)((o / n) % L);
+        const int64_t row = o / Ln;
+        const uint64_t q = (uint64_t)qs[l];
+        const int64_t c0_row = row * 2 * Ln + (int64_t)l * n;
+        const Vec a = *reinterpret_cast<const Vec*>(ks0 + o);
+        const Vec b = *reinterpret_cast<const Vec*>(ks1 + o);
+        Vec y;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int64_t src = (int64_t)perm[k0 + k] & (n - 1);
+            y.v[k] = (int64_t)addmod_u64((uint64_t)ct[c0_row + src],
+                                         (uint64_t)a.v[k], q);
+        }
+        *reinterpret_cast<Vec*>(out + c0_row + k0) = y;
+        *reinterpret_cast<Vec*>(out + c0_row + Ln + k0) = b;
+    }
+}
+
 inline bool aligned16(const void* p) {
     return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
 }
@@ -1364,6 +1459,104 @@ torch::Tensor pdec_share(torch::Tensor ct, torch::Tensor s_hat,
                            out.data_ptr<int64_t>(), tv, n, (int)L,
                            add_c0 ? 1 : 0, qs.data_ptr<int64_t>(),
                            ratios.data_ptr<int64_t>());
+    }
+    return out;
+}
+
+// c [..., D, n] coefficient-domain digits -> sigma_g digits lifted into the
+// Lp = qs.numel() gathered limbs: [..., D, Lp, n]. ginv = g^-1 mod 2n.
+torch::Tensor galois_lift(torch::Tensor c, int64_t ginv, torch::Tensor qs,
+                          torch::Tensor ratios) {
+    CHECK_CUDA_OK(c);
+    CHECK_CUDA_OK(qs);
+    CHECK_CUDA_OK(ratios);
+    TORCH_CHECK(c.is_contiguous() && qs.is_contiguous() &&
+                ratios.is_contiguous());
+    TORCH_CHECK(c.dtype() == torch::kInt64 && qs.dtype() == torch::kInt64 &&
+                ratios.dtype() == torch::kInt64);
+    TORCH_CHECK(c.dim() >= 2, "c must be [.., D, n]");
+    const int64_t D = c.size(-2);
+    const int64_t n = c.size(-1);
+    const int64_t Lp = qs.numel();
+    TORCH_CHECK(n >= 1 && (n & (n - 1)) == 0, "n must be a power of two");
+    TORCH_CHECK(D >= 1 && Lp >= D && ratios.numel() == 2 * Lp,
+                "need prime / ratio tables for the D digits plus the targets");
+    TORCH_CHECK(ginv >= 1 && ginv < 2 * n && (ginv & 1),
+                "ginv must be an odd residue mod 2n");
+    auto sizes = c.sizes().vec();
+    sizes.insert(sizes.end() - 1, Lp);
+    auto out = torch::empty(sizes, c.options());
+    const int64_t total = c.numel();
+    if (total == 0) return out;
+    auto stream = at::cuda::getCurrentCUDAStream();
+    // c is only gathered (8-byte reads, any alignment); the 16-byte stores go
+    // to the fresh allocation, so only n = 1 takes the scalar kernel
+    const bool vec2 = n % 2 == 0 && aligned16(out.data_ptr<int64_t>());
+    const int64_t tv = vec2 ? total / 2 : total;
+    int blocks = (int)std::min<int64_t>((tv + kThreads - 1) / kThreads, 4096);
+    if (vec2) {
+        hipLaunchKernelGGL(galois_lift_kernel<2>, dim3(blocks), dim3(kThreads),
+                           0, stream, c.data_ptr<int64_t>(),
+                           out.data_ptr<int64_t>(), tv, n, (int)D, (int)Lp,
+                           ginv, qs.data_ptr<int64_t>(),
+                           ratios.data_ptr<int64_t>());
+    } else {
+        hipLaunchKernelGGL(galois_lift_kernel<1>, dim3(blocks), dim3(kThreads),
+                           0, stream, c.data_ptr<int64_t>(),
+                           out.data_ptr<int64_t>(), tv, n, (int)D, (int)Lp,
+                           ginv, qs.data_ptr<int64_t>(),
+                           ratios.data_ptr<int64_t>());
+    }
+    return out;
+}
+
+// ct [..., 2, L, n], ks0 / ks1 [..., L, n], perm int32 [n] -> rotated
+// ciphertext [..., 2, L, n] = (c0[perm] + ks0, ks1).
+torch::Tensor galois_perm_add(torch::Tensor ct, torch::Tensor ks0,
+                              torch::Tensor ks1, torch::Tensor perm,
+                              torch::Tensor qs) {
+    CHECK_CUDA_OK(ct);
+    CHECK_CUDA_OK(ks0);
+    CHECK_CUDA_OK(ks1);
+    CHECK_CUDA_OK(perm);
+    CHECK_CUDA_OK(qs);
+    TORCH_CHECK(ct.is_contiguous() && ks0.is_contiguous() &&
+                ks1.is_contiguous() && perm.is_contiguous() &&
+                qs.is_contiguous());
+    TORCH_CHECK(ct.dtype() == torch::kInt64 && ks0.dtype() == torch::kInt64 &&
+                ks1.dtype() == torch::kInt64 && qs.dtype() == torch::kInt64 &&
+                perm.dtype() == torch::kInt32);
+    TORCH_CHECK(ct.dim() >= 3 && ct.size(-3) == 2, "ct must be [.., 2, L, n]");
+    const int64_t L = ct.size(-2);
+    const int64_t n = ct.size(-1);
+    TORCH_CHECK(n >= 1 && (n & (n - 1)) == 0, "n must be a power of two");
+    TORCH_CHECK(L >= 1 && qs.numel() >= L, "limb count exceeds the prime table");
+    TORCH_CHECK(perm.numel() == n, "perm must be int32 [n]");
+    auto sizes = ct.sizes().vec();
+    sizes.erase(sizes.end() - 3);  // drop the (c0, c1) dim
+    TORCH_CHECK(ks0.sizes().vec() == sizes && ks1.sizes().vec() == sizes,
+                "ks0 / ks1 must be [.., L, n]");
+    auto out = torch::empty_like(ct);
+    const int64_t total = ks0.numel();
+    if (total == 0) return out;
+    auto stream = at::cuda::getCurrentCUDAStream();
+    const bool vec2 = n % 2 == 0 && aligned16(ks0.data_ptr<int64_t>()) &&
+                      aligned16(ks1.data_ptr<int64_t>()) &&
+                      aligned16(out.data_ptr<int64_t>());
+    const int64_t tv = vec2 ? total / 2 : total;
+    int blocks = (int)std::min<int64_t>((tv + kThreads - 1) / kThreads, 4096);
+    if (vec2) {
+        hipLaunchKernelGGL(galois_perm_add_kernel<2>, dim3(blocks),
+                           dim3(kThreads), 0, stream, ct.data_ptr<int64_t>(),
+                           ks0.data_ptr<int64_t>(), ks1.data_ptr<int64_t>(),
+                           perm.data_ptr<int32_t>(), out.data_ptr<int64_t>(),
+                           tv, n, (int)L, qs.data_ptr<int64_t>());
+    } else {
+        hipLaunchKernelGGL(galois_perm_add_kernel<1>, dim3(blocks),
+                           dim3(kThreads), 0, stream, ct.data_ptr<int64_t>(),
+                           ks0.data_ptr<int64_t>(), ks1.data_ptr<int64_t>(),
+                           perm.data_ptr<int32_t>(), out.data_ptr<int64_t>(),
+                           tv, n, (int)L, qs.data_ptr<int64_t>());
     }
     return out;
 }

@@ -16,8 +16,9 @@ SUM over <= 8 clients cannot overflow (lazy reduction; hefl/fl/secure.py).
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import Dict, Iterable, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -216,6 +217,79 @@ class GpuBackend:
                                   e_hat.contiguous(), bool(add_c0), self.qs,
                                   self.ratio_words)
 
+    # ----- level-aware key-switch + slot rotation (CKKSContext.rotate) -----
+    def level_tables(self, l: int) -> "LevelTables":
+        """Prime / twiddle tables gathered at rows [0..l-1, L] — the limbs a
+        key-switch at level l runs over (l chain primes + the special prime,
+        which is the last row) — plus the mod-down scalars P^-1 mod q_i.
+        Gathered once per level; every kernel takes its tables as arguments,
+        so a level-l key-switch is the top-level launch sequence on these."""
+        cache = self.__dict__.setdefault("_level_tables", {})
+        if l not in cache:
+            sp = len(self.primes) - 1
+            if not 1 <= l <= sp:
+                raise ValueError(f"level must be in [1, {sp}], got {l}")
+            idx = torch.tensor(list(range(l)) + [sp], dtype=torch.int64,
+                               device=self.device)
+            P = self.primes[sp]
+            pinv = [pow(P % q, -1, q) for q in self.primes[:l]]
+            pinv_sh = [np.int64(np.uint64((v << 64) // q))
+                       for v, q in zip(pinv, self.primes[:l])]
+            cache[l] = LevelTables(
+                idx=idx,
+                w=self.w.index_select(0, idx),
+                w_shoup=self.w_shoup.index_select(0, idx),
+                qs=self.qs.index_select(0, idx),
+                ratio_words=self.ratio_words.index_select(0, idx),
+                pinv=torch.tensor(pinv, dtype=torch.int64, device=self.device),
+                pinv_shoup=torch.tensor(np.array(pinv_sh, dtype=np.int64),
+                                        device=self.device))
+        return cache[l]
+
+    def ntt_level_(self, x: torch.Tensor, tb: "LevelTables") -> torch.Tensor:
+        """In-place forward NTT of a contiguous [..., l+1, n] tensor the
+        caller owns, over the gathered limbs of `tb`."""
+        Lp = tb.qs.numel()
+        self._C.ntt_limbs(x.view(-1, Lp, self.n), tb.w, tb.w_shoup, tb.qs, Lp)
+        return x
+
+    def galois_lift(self, c: torch.Tensor, ginv: int,
+                    tb: "LevelTables") -> torch.Tensor:
+        """c [..., l, n] coefficient-domain digits -> sigma_g(c) lifted into
+        the l+1 limbs of `tb`: [..., l, l+1, n]. One launch."""
+        return self._C.galois_lift(c.contiguous(), int(ginv), tb.qs,
+                                   tb.ratio_words)
+
+    def galois_perm_add(self, ct: torch.Tensor, ks0: torch.Tensor,
+                        ks1: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
+        """(ct[.., 0][perm] + ks0, ks1) assembled as [..., 2, l, n], c0 read
+        in place. One launch."""
+        return self._C.galois_perm_add(ct.contiguous(), ks0.contiguous(),
+                                       ks1.contiguous(), perm, self.qs)
+
+
+@dataclass
+class LevelTables:
+    """Device tables of the l+1 limbs {q_0..q_{l-1}, P} of one level."""
+    idx: torch.Tensor          # int64 [l+1] rows of the full tables
+    w: torch.Tensor            # [l+1, n]
+    w_shoup: torch.Tensor
+    qs: torch.Tensor           # [l+1]
+    ratio_words: torch.Tensor  # [l+1, 2]
+    pinv: torch.Tensor         # [l] P^-1 mod q_i
+    pinv_shoup: torch.Tensor
+
+
+@dataclass
+class GaloisTables:
+    """Index tables of one Galois element g (sigma_g: a(X) -> a(X^g))."""
+    g: int
+    ginv: int                  # g^-1 mod 2n
+    perm: torch.Tensor         # int64 [n]: NTT domain, out[k] = in[perm[k]]
+    perm32: torch.Tensor       # int32 copy for the HIP kernel
+    src: torch.Tensor          # int64 [n]: coefficient domain source index
+    neg: torch.Tensor          # bool [n]: source enters negated
+
 
 # ---------------------------------------------------------------------------
 # Data containers
@@ -259,6 +333,7 @@ class KeyPair:
                               # party's share, or None where none is held)
     pk: torch.Tensor          # int64 [2, L, n] NTT form: (b, a)
     relin: Optional[torch.Tensor] = None  # [dnum, 2, L, n] later
+    galois: Optional[dict] = None  # Galois element -> key [L, 2, L+1, n]
 
 
 @dataclass
@@ -921,6 +996,324 @@ class CKKSContext:
         c0 = self._modadd(d0, ks0, limbs)
         c1 = self._modadd(d1, ks1, limbs)
         return Ciphertext(torch.stack([c0, c1], dim=-3), a.scale * b.scale)
+
+    # ----- slot rotation / conjugation (Galois automorphisms) -----
+    # sigma_g: a(X) -> a(X^g). With this encoder's 5^j slot ordering, g = 5^r
+    # moves slot (j + r) mod slots into slot j — a LEFT rotation, decoded
+    # np.roll(v, -r) — and g = 2n - 1 conjugates every slot. sigma_g(ct)
+    # decrypts under sigma_g(s); a key-switch through the Galois key for g
+    # (an encryption of P*q~_d*sigma_g(s) per digit d) brings it back under s.
+    def galois_element(self, step: Optional[int] = None,
+                       conjugate: bool = False) -> int:
+        """Galois element of a rotation by `step` slots, or of conjugation."""
+        if conjugate:
+            if step is not None:
+                raise ValueError("pass either a step or conjugate=True, not both")
+            return 2 * self.n - 1
+        if step is None:
+            raise ValueError("galois_element needs a step or conjugate=True")
+        return pow(5, int(step) % self.slots, 2 * self.n)
+
+    def _galois_tables(self, g: int) -> GaloisTables:
+        """Host-computed index tables of sigma_g, cached on the device."""
+        cache = self.__dict__.setdefault("_galois_cache", {})
+        if g not in cache:
+            n, two_n = self.n, 2 * self.n
+            if not (0 < g < two_n and g % 2 == 1):
+                raise ValueError(f"Galois element must be odd in (0, {two_n}), got {g}")
+            logn = n.bit_length() - 1
+
+            def brv(v):
+                r = np.zeros_like(v)
+                for b in range(logn):
+                    r |= ((v >> b) & 1) << (logn - 1 - b)
+                return r
+
+            k = np.arange(n, dtype=np.int64)
+            # NTT slot k evaluates at psi^(2*brv(k)+1); sigma_g sends the
+            # value at psi^(e*g) to the slot of psi^e
+            perm = brv((((2 * brv(k) + 1) * g) % two_n - 1) // 2)
+            ginv = pow(g, -1, two_n)
+            # coefficient k of sigma_g(a) is +-a_j with j*g = k (mod n)
+            e = (k * ginv) % two_n
+            dev = self.device
+            cache[g] = GaloisTables(
+                g=g, ginv=ginv,
+                perm=torch.from_numpy(perm).to(dev),
+                perm32=torch.from_numpy(perm.astype(np.int32)).to(dev),
+                src=torch.from_numpy(e % n).to(dev),
+                neg=torch.from_numpy(e >= n).to(dev))
+        return cache[g]
+
+    def default_rotation_steps(self) -> List[int]:
+        """+-2^k for k = 0 .. log2(slots)-1: every step composes from these
+        in at most ~log2(slots)/2 hops (non-adjacent form)."""
+        steps = []
+        k = 1
+        while k < self.slots:
+            steps += [k, -k]
+            k *= 2
+        return steps
+
+    def galois_keygen(self, sk: torch.Tensor,
+                      steps: Optional[Iterable[int]] = None,
+                      conjugate: bool = False) -> Dict[int, torch.Tensor]:
+        """Galois keys {element g: int64 [L, 2, L+1, n]}, one per rotation
+        step (default: +-2^k) plus conjugation on request.
+
+        Same shape and distribution as relin_keygen's output; digit d hides
+        P*q~_d*sigma_g(s) instead of P*q~_d*s^2 — in RNS (P mod q_d) *
+        sigma_g(s) at limb d and nothing elsewhere. Sampled on the host from
+        the context's seeded stream like every key, so all ranks and the CPU
+        and GPU contexts derive identical keys."""
+        if sk is None:
+            raise ValueError(
+                "galois_keygen needs the secret key; under key_mode="
+                "'threshold' no party holds s, so Galois keys are unsupported")
+        steps = self.default_rotation_steps() if steps is None else list(steps)
+        elements = [self.galois_element(s) for s in steps]
+        if conjugate:
+            elements.append(self.galois_element(conjugate=True))
+        L, n = self.L, self.n
+        Lp = L + 1
+        P = self.special
+        sk_ext = self._sk_extended(sk)            # [L+1, n]
+        keys: Dict[int, torch.Tensor] = {}
+        for g in elements:
+            if g == 1 or g in keys:               # step 0 / duplicate step
+                continue
+            perm = self._galois_tables(g).perm
+            s_g = sk_ext.index_select(-1, perm)   # sigma_g(s), NTT form
+            gk = torch.empty((L, 2, Lp, n), dtype=torch.int64,
+                             device=self.device)
+            for d in range(L):
+                a = self._sample_uniform((Lp, n)).to(self.device)
+                e = self._to_rns_ntt(self._sample_err((n,), host=True), Lp)
+                for i in range(Lp):
+                    q = self._q(i)
+                    b = torch.remainder(-(self.backend.modmul(a[i], sk_ext[i], i)
+                                          + e[i]), q)
+                    if i == d:
+                        b = torch.remainder(
+                            b + self.backend.modmul_scalar(s_g[i], P % q, i), q)
+                    gk[d, 0, i] = b
+                    gk[d, 1, i] = a[i]
+            keys[g] = gk
+        return keys
+
+    def _key_at_level(self, key: torch.Tensor, l: int) -> torch.Tensor:
+        """Digits 0..l-1 and limbs {0..l-1, L} of a switching key — exact,
+        because q~_d = delta_{d,i} holds over any prefix of the chain."""
+        if l == self.L:
+            return key.contiguous()
+        cache = self.__dict__.setdefault("_key_level_cache", {})
+        ck = (key.data_ptr(), l)
+        hit = cache.get(ck)
+        if hit is None or hit[0] is not key:
+            idx = torch.tensor(list(range(l)) + [self.L], dtype=torch.int64,
+                               device=key.device)
+            # the cache entry holds `key` itself so its storage (and with it
+            # the data_ptr the entry is filed under) cannot be reused
+            hit = (key, key[:l].index_select(2, idx).contiguous())
+            cache[ck] = hit
+        return hit[1]
+
+    @staticmethod
+    def _coeff_automorphism(c: torch.Tensor, q, gt: GaloisTables) -> torch.Tensor:
+        """sigma_g on coefficient rows c [..., n] of residues in [0, q) (q an
+        int or a tensor broadcasting over c): gather, then negate mod q where
+        the source wrapped past X^n. A negated zero stays zero."""
+        v = torch.index_select(c, -1, gt.src)
+        return torch.where(gt.neg & (v != 0), q - v, v)
+
+    @staticmethod
+    def _galois_fused() -> bool:
+        """HEFL_GALOIS_FUSED=0 archives the fused kernels behind the path
+        composed of torch gather / where / stack (PERFORMANCE.md: slower)."""
+        return os.getenv("HEFL_GALOIS_FUSED", "1") != "0"
+
+    def _keyswitch_level(self, x: torch.Tensor, key: torch.Tensor, l: int,
+                         g: Optional[int] = None):
+        """Level-aware hybrid key-switch of NTT-form x [..., l, n] (l <= L
+        chain limbs) through `key` [L, 2, L+1, n]; returns (ks0, ks1), each
+        [..., l, n]. Uses digits 0..l-1 of the key over the limbs
+        {q_0..q_{l-1}, P}. With g given, switches sigma_g(x) instead — the
+        automorphism is applied to the coefficient-domain digits on the way.
+
+        GPU: the launch sequence of _keyswitch on tables gathered at rows
+        [0..l-1, L] (GpuBackend.level_tables)."""
+        if x.shape[-2] != l or not 1 <= l <= self.L:
+            raise ValueError(f"expected [.., {l}, n] with 1 <= l <= {self.L}, "
+                             f"got {tuple(x.shape)}")
+        if tuple(key.shape) != (self.L, 2, self.L + 1, self.n):
+            raise ValueError(
+                f"switching key must be [{self.L}, 2, {self.L + 1}, {self.n}], "
+                f"got {tuple(key.shape)}")
+        n, P = self.n, self.special
+        gt = None if g is None else self._galois_tables(g)
+        idx = list(range(l)) + [self.L]
+        if self.device.type == "cuda":
+            be = self.backend
+            tb = be.level_tables(l)
+            kl = self._key_at_level(key, l)
+            c = be.ntt_all(x, inverse=True)            # digits -> coeff domain
+            if gt is None:
+                dig = be._C.bcast_center_mod(c, 0, tb.qs, tb.ratio_words, l + 1)
+            elif self._galois_fused():
+                dig = be.galois_lift(c, gt.ginv, tb)
+            else:
+                c = self._coeff_automorphism(c, be.qs[:l].view(l, 1), gt)
+                dig = be._C.bcast_center_mod(c.contiguous(), 0, tb.qs,
+                                             tb.ratio_words, l + 1)
+            be.ntt_level_(dig, tb)                     # [..., l, l+1, n]
+            acc0, acc1 = be._C.ks_inner(dig, kl, tb.qs, tb.ratio_words,
+                                        l, l + 1, n)
+            outs = []
+            for acc in (acc0, acc1):
+                cl = be.ntt(acc[..., l, :], self.L, inverse=True)
+                r_ntt = be.ntt_all(be.bcast_center_mod(cl, P, l))
+                diff = be.modsub_limbs(acc, r_ntt, l)
+                outs.append(be._C.modmul_scalar_limbs(
+                    diff, tb.pinv, tb.pinv_shoup, be.qs, l, n))
+            return outs[0], outs[1]
+        lead = x.shape[:-2]
+        acc0 = torch.zeros(lead + (l + 1, n), dtype=torch.int64, device=x.device)
+        acc1 = torch.zeros_like(acc0)
+        for d in range(l):
+            # digit d: residues mod q_d in [0, q_d), lifted to every limb
+            c = self.backend.ntt(x[..., d, :], d, inverse=True)
+            if gt is not None:
+                c = self._coeff_automorphism(c, self._q(d), gt)
+            for j, i in enumerate(idx):
+                q = self._q(i)
+                dig = self.backend.ntt(torch.remainder(c, q), i)
+                acc0[..., j, :] = torch.remainder(
+                    acc0[..., j, :] + self.backend.modmul(
+                        dig, key[d, 0, i].expand_as(dig).contiguous(), i), q)
+                acc1[..., j, :] = torch.remainder(
+                    acc1[..., j, :] + self.backend.modmul(
+                        dig, key[d, 1, i].expand_as(dig).contiguous(), i), q)
+        # mod-down by P, as in _keyswitch: P sits at position l here
+        P_half = P // 2
+        outs = []
+        for acc in (acc0, acc1):
+            cl = self.backend.ntt(acc[..., l, :], self.L, inverse=True)
+            cl_c = torch.where(cl > P_half, cl - P, cl)
+            out = acc[..., :l, :].clone()
+            for i in range(l):
+                q = self._q(i)
+                r_ntt = self.backend.ntt(torch.remainder(cl_c, q), i)
+                diff = torch.remainder(out[..., i, :] - r_ntt, q)
+                out[..., i, :] = self.backend.modmul_scalar(
+                    diff, pow(P % q, -1, q), i)
+            outs.append(out)
+        return outs[0], outs[1]
+
+    def _apply_galois_data(self, data: torch.Tensor, g: int,
+                           key: torch.Tensor) -> torch.Tensor:
+        """sigma_g on ct data [..., 2, l, n]: (sigma_g(c0) + ks0, ks1) with
+        (ks0, ks1) the key-switch of sigma_g(c1). c0 is permuted in the NTT
+        domain, where sigma_g is a pure permutation."""
+        l = data.shape[-2]
+        gt = self._galois_tables(g)
+        ks0, ks1 = self._keyswitch_level(data[..., 1, :, :], key, l, g=g)
+        if self.device.type == "cuda":
+            be = self.backend
+            if self._galois_fused():
+                return be.galois_perm_add(data, ks0, ks1, gt.perm32)
+            c0 = torch.index_select(data[..., 0, :, :], -1, gt.perm)
+            return torch.stack([be.modadd_limbs(c0, ks0), ks1], dim=-3)
+        c0 = torch.index_select(data[..., 0, :, :], -1, gt.perm)
+        return torch.stack([self._modadd(c0, ks0, list(range(l))), ks1], dim=-3)
+
+    @staticmethod
+    def _naf(v: int) -> List[int]:
+        """Signed powers of two summing to v, no two adjacent (NAF)."""
+        out, k = [], 0
+        while v:
+            if v & 1:
+                d = 2 - (v & 3)       # +1 or -1
+                out.append(d << k)
+                v -= d
+            v >>= 1
+            k += 1
+        return out
+
+    def _rotation_hops(self, step: int, gk) -> List[int]:
+        """Galois elements to apply, in order, for a rotation by `step`."""
+        s = int(step) % self.slots
+        if s == 0:
+            return []
+        gk = gk or {}
+        g = self.galois_element(s)
+        if g in gk:
+            return [g]
+        signed = s if s <= self.slots // 2 else s - self.slots
+        hops = []
+        for h in self._naf(signed):
+            gh = self.galois_element(h)
+            if gh not in gk:
+                raise ValueError(
+                    f"rotation by {step} needs the Galois key for step {h} — "
+                    f"run galois_keygen(sk, steps=[{h}]) (Pyfhel API: "
+                    f"rotateKeyGen) first")
+            hops.append(gh)
+        return hops
+
+    def rotate_data(self, data: torch.Tensor, step: int, gk) -> torch.Tensor:
+        """Rotate ct data [..., 2, l, n] left by `step` slots (any level
+        1..L, any batch shape). One key-switch when gk holds the exact key,
+        else one per non-adjacent-form digit over the +-2^k keys."""
+        hops = self._rotation_hops(step, gk)
+        if not hops:
+            return data.clone()
+        for g in hops:
+            data = self._apply_galois_data(data, g, gk[g])
+        return data
+
+    def conjugate_data(self, data: torch.Tensor, gk) -> torch.Tensor:
+        g = self.galois_element(conjugate=True)
+        if not gk or g not in gk:
+            raise ValueError(
+                "conjugation needs its Galois key — run galois_keygen(sk, "
+                "conjugate=True) (Pyfhel API: rotateKeyGen) first")
+        return self._apply_galois_data(data, g, gk[g])
+
+    def sum_slots_data(self, data: torch.Tensor, gk, width: int) -> torch.Tensor:
+        """log2(width) rotate-and-add rounds: slot j ends up holding
+        sum_{t < width} v[(j + t) mod slots]."""
+        if width < 1 or width & (width - 1) or width > self.slots:
+            raise ValueError(f"width must be a power of two <= {self.slots}, "
+                             f"got {width}")
+        limbs = list(range(data.shape[-2]))
+        k = 1
+        while k < width:
+            data = self._modadd(data, self.rotate_data(data, k, gk), limbs)
+            k *= 2
+        return data
+
+    def rotate(self, ct: Ciphertext, step: int, gk) -> Ciphertext:
+        """Slot j of the result holds old slot (j + step) mod slots: decoded,
+        np.roll(v, -step). Scale and level are unchanged."""
+        return Ciphertext(self.rotate_data(ct.data, step, gk), ct.scale)
+
+    def conjugate(self, ct: Ciphertext, gk) -> Ciphertext:
+        return Ciphertext(self.conjugate_data(ct.data, gk), ct.scale)
+
+    def sum_slots(self, ct: Ciphertext, gk, width: int) -> Ciphertext:
+        return Ciphertext(self.sum_slots_data(ct.data, gk, width), ct.scale)
+
+    def rotate_tensor(self, ct: CtxtTensor, step: int, gk) -> CtxtTensor:
+        """Rotate every ciphertext of the batch by the same step."""
+        return CtxtTensor(self.rotate_data(ct.data, step, gk), ct.scale,
+                          ct.count)
+
+    def conjugate_tensor(self, ct: CtxtTensor, gk) -> CtxtTensor:
+        return CtxtTensor(self.conjugate_data(ct.data, gk), ct.scale, ct.count)
+
+    def sum_slots_tensor(self, ct: CtxtTensor, gk, width: int) -> CtxtTensor:
+        return CtxtTensor(self.sum_slots_data(ct.data, gk, width), ct.scale,
+                          ct.count)
 
     def modreduce_tensor_(self, ct: CtxtTensor) -> CtxtTensor:
         """Reduce lazily-summed (int64) limb values back to [0, q_i) in place

@@ -95,6 +95,17 @@ class PyCtxt:
 
     __rmul__ = __mul__
 
+    # ----- slot rotation: ct << k moves slot j+k into slot j (left) -----
+    def __lshift__(self, k):
+        if isinstance(k, (int, np.integer)):
+            return self._he().rotate(self, int(k))
+        return NotImplemented
+
+    def __rshift__(self, k):
+        if isinstance(k, (int, np.integer)):
+            return self._he().rotate(self, -int(k))
+        return NotImplemented
+
     # ----- pickling: standalone, context params embedded -----
     def __getstate__(self):
         he = self._pyfhel
@@ -172,6 +183,43 @@ class Pyfhel:
             self._keys = KeyPair(sk=self._sk, pk=self._pk)
         self._keys.relin = self.context.relin_keygen(self._sk)
 
+    def rotateKeyGen(self, bitCount: int = 1, steps=None,
+                     conjugate: bool = True):
+        """Generate Galois keys for slot rotation (default steps: +-2^k,
+        from which any step composes) and, by default, conjugation.
+        `bitCount` is accepted for Pyfhel signature parity and ignored:
+        the digits are the RNS limbs."""
+        if self._sk is None:
+            raise ValueError("keyGen must run before rotateKeyGen")
+        if self._keys is None:  # keys restored from bytes, not keyGen()
+            self._keys = KeyPair(sk=self._sk, pk=self._pk)
+        gk = self.context.galois_keygen(self._sk, steps=steps,
+                                        conjugate=conjugate)
+        if self._keys.galois:   # a later call adds to the keys already held
+            gk = {**self._keys.galois, **gk}
+        self._keys.galois = gk
+
+    @property
+    def _galois(self):
+        return None if self._keys is None else self._keys.galois
+
+    def _set_galois(self, gk):
+        if self._keys is None:
+            self._keys = KeyPair(sk=self._sk, pk=self._pk)
+        self._keys.galois = gk
+
+    def rotate(self, ct, k: int):
+        """Rotate a PyCtxt or a CtxtTensor left by k slots (k < 0: right)."""
+        if isinstance(ct, CtxtTensor):
+            return self.context.rotate_tensor(ct, k, self._galois)
+        return PyCtxt(self.context.rotate(ct._ct, k, self._galois), self)
+
+    def conjugate(self, ct):
+        """Complex-conjugate every slot of a PyCtxt or a CtxtTensor."""
+        if isinstance(ct, CtxtTensor):
+            return self.context.conjugate_tensor(ct, self._galois)
+        return PyCtxt(self.context.conjugate(ct._ct, self._galois), self)
+
     # ----- scalar API (reference-exact shape) -----
     def encryptFrac(self, value: float) -> PyCtxt:
         """One scalar -> one ciphertext (reference FLPyfhelin.py:217).
@@ -235,6 +283,32 @@ class Pyfhel:
     def from_bytes_secretKey(self, buf: bytes):
         self._sk = self._key_from_bytes(b"SK\x00\x00", buf)
 
+    def to_bytes_rotateKey(self) -> bytes:
+        """Versioned header (kind GK), key count, then per key its Galois
+        element (u64) and the tensor as one .npy record."""
+        gk = self._galois
+        if not gk:
+            raise ValueError("no rotation keys — run rotateKeyGen first")
+        body = io.BytesIO()
+        body.write(struct.pack("<I", len(gk)))
+        for g, t in gk.items():
+            body.write(struct.pack("<Q", int(g)))
+            np.save(body, t.cpu().numpy(), allow_pickle=False)
+        return _pack_header(b"GK\x00\x00", self.context.cfg) + body.getvalue()
+
+    def from_bytes_rotateKey(self, buf: bytes):
+        cfg, off = _unpack_header(buf, b"GK\x00\x00")
+        if self._ctx is None:
+            self.contextGen_cfg(cfg, device=self._device)
+        body = io.BytesIO(buf[off:])
+        (count,) = struct.unpack("<I", body.read(4))
+        gk = {}
+        for _ in range(count):
+            (g,) = struct.unpack("<Q", body.read(8))
+            arr = np.load(body, allow_pickle=False)
+            gk[int(g)] = torch.from_numpy(arr).to(self.context.device)
+        self._set_galois(gk)
+
     # Pyfhel pickles whole objects in the reference's export dict
     # (FLPyfhelin.py:233); support that directly. The SECRET key is never
     # pickled: the reference's C-backed pickled Pyfhel carries no usable key
@@ -248,6 +322,9 @@ class Pyfhel:
             state["cfg"] = self._ctx.cfg
         if self._pk is not None:
             state["pk"] = self._pk.cpu().numpy()
+        if self._galois:  # evaluation keys are public, like pk
+            state["galois"] = {int(g): t.cpu().numpy()
+                               for g, t in self._galois.items()}
         return state
 
     def __setstate__(self, state):
@@ -258,3 +335,6 @@ class Pyfhel:
             self._pk = torch.from_numpy(state["pk"])
         if state.get("sk") is not None:  # legacy pickles only
             self._sk = torch.from_numpy(state["sk"])
+        if state.get("galois"):  # absent from pickles made before rotation
+            self._set_galois({int(g): torch.from_numpy(a)
+                              for g, a in state["galois"].items()})
