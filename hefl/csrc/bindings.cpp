@@ -2,6 +2,7 @@
 // CKKS NTT/pointwise (ntt.hip) + CNN training ops (cnn.hip).
 #include <torch/extension.h>
 
+#include <tuple>
 #include <vector>
 
 // ntt.hip
@@ -68,6 +69,9 @@ torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,
 torch::Tensor linear_dgrad(torch::Tensor dy, torch::Tensor w);
 torch::Tensor linear_wgrad(torch::Tensor dy, torch::Tensor x);
 std::vector<torch::Tensor> maxpool2x2_fwd(torch::Tensor x);
+std::tuple<torch::Tensor, torch::Tensor, int64_t, int64_t>
+conv2d_relu_pool_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,
+                     int64_t pad);
 torch::Tensor synth_batch(torch::Tensor templates, torch::Tensor labels,
                           int64_t seed, double zoom, double shear,
                           int64_t flip);
@@ -187,6 +191,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("linear_dgrad", &linear_dgrad);
     m.def("linear_wgrad", &linear_wgrad);
     m.def("maxpool2x2_fwd", &maxpool2x2_fwd);
+    m.def("conv2d_relu_pool_fwd", &conv2d_relu_pool_fwd);
     m.def("synth_batch", &synth_batch, py::arg("templates"), py::arg("labels"),
           py::arg("seed"), py::arg("zoom") = 0.0, py::arg("shear") = 0.0,
           py::arg("flip") = 0);

@@ -17,6 +17,10 @@
 //   glds16                         global_load_lds 16-B DMA helper
 //   conv_fwd_glds_kernel           fwd with LDS-DMA 3-buffer counted-vmcnt
 //                                  pipeline (raw s_barrier, 1 stage in flight)
+//   ...<POOL=true> of both         conv+bias+ReLU+maxpool2x2 in one launch:
+//                                  pool-window-major M rows, 3 register
+//                                  compares in the epilogue
+//                                  (conv2d_relu_pool_fwd)
 //   conv_dgrad_kernel/_glds_       dgrad, K reordered to (r,s,ko) for
 //                                  contiguous dy gathers
 //   conv_wgrad_kernel/_glds_       wgrad, pixel-major tiles, split-K slabs
@@ -76,6 +80,7 @@
 #include <ATen/cuda/CUDAContext.h>
 
 #include <algorithm>
+#include <tuple>
 #include <unordered_map>
 
 #define CHECK_GPU(x) TORCH_CHECK((x).is_cuda(), #x " must be on GPU")
@@ -313,12 +318,60 @@ __device__ __forceinline__ void zero16(unsigned short* dst) {
 
 // ---- forward: y[m=(n,oh,ow), ko] = sum_k A(m,k) * w[ko, k],
 //      k = (r, s, c) with c fastest ----
-template <int BM, int BN, int WM, int WN, int FM, int FN>
+//
+// POOL = true fuses the 2x2/2 max-pool into the epilogue (ReLU always on,
+// stride 1). The M rows are enumerated pool-window-major,
+//   m = ((n*PH + ph)*PW + pw)*4 + q,  oh = 2*ph + (q>>1),  ow = 2*pw + (q&1),
+// so the four cells of a window are the four accumulator registers of one
+// lane (D rows (lane>>4)*4 + r) and the pool is three register compares:
+// no LDS, no cross-lane traffic. BM and the fragment row groups are
+// multiples of 4, so a window never straddles a lane, fragment or tile.
+// Rows/columns the floor-pool drops (odd OH/OW) are never enumerated.
+// y receives the pooled [N,PH,PW,Kout] bf16 tensor and pidx the argmax
+// (0..3, first maximum wins exactly like maxpool_fwd_oct_kernel).
+
+// Window-major row decode shared by the POOL instantiations.
+__device__ __forceinline__ void pool_row_decode(int am, int PH, int PW, int& n,
+                                                int& oh, int& ow) {
+    const int win = am >> 2, q = am & 3;
+    n = win / (PH * PW);
+    const int rem = win % (PH * PW);
+    const int ph = rem / PW;
+    oh = 2 * ph + (q >> 1);
+    ow = 2 * (rem - ph * PW) + (q & 1);
+}
+
+// bias + ReLU + bf16 rounding of the four window cells of one accumulator
+// fragment, then the first-max-wins compare chain on the ROUNDED values
+// (what the separate pool kernel would read back from y).
+__device__ __forceinline__ void pool_epilogue_store(
+    f32x4 acc, float bv, unsigned short* __restrict__ p,
+    uint8_t* __restrict__ pidx, int64_t o) {
+    unsigned short u[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        float v = acc[r] + bv;
+        u[r] = f2bf(v > 0.f ? v : 0.f);
+    }
+    unsigned short bu = u[0];
+    float best = bf2f(u[0]);
+    int bi = 0;
+#pragma unroll
+    for (int r = 1; r < 4; ++r) {
+        const float v = bf2f(u[r]);
+        if (v > best) { best = v; bu = u[r]; bi = r; }
+    }
+    p[o] = bu;
+    pidx[o] = (uint8_t)bi;
+}
+
+template <int BM, int BN, int WM, int WN, int FM, int FN, bool POOL = false>
 __global__ void __launch_bounds__(TPB)
 conv_fwd_kernel(const unsigned short* __restrict__ x,
                 const unsigned short* __restrict__ w,
                 const float* __restrict__ bias, unsigned short* __restrict__ y,
-                ConvShape s, int relu) {
+                uint8_t* __restrict__ pidx, ConvShape s, int relu) {
+    static_assert(!POOL || (BM % 4 == 0), "pool windows must not straddle tiles");
     __shared__ ConvTile<BM, BN, WM, WN, FM, FN> sm;
     constexpr int RPT = BM * 4 / TPB;  // A-chunks per thread
     const int tid = threadIdx.x;
@@ -326,7 +379,8 @@ conv_fwd_kernel(const unsigned short* __restrict__ x,
     const int lane = tid & 63;
     const int m0 = blockIdx.x * BM;
     const int n0 = blockIdx.y * BN;
-    const int M = s.N * s.OH * s.OW;
+    const int PH = s.OH >> 1, PW = s.OW >> 1;  // POOL only
+    const int M = POOL ? s.N * PH * PW * 4 : s.N * s.OH * s.OW;
     const int KK = s.R * s.S * s.C;
     const bool fast = (s.C % 8 == 0);
 
@@ -340,10 +394,14 @@ conv_fwd_kernel(const unsigned short* __restrict__ x,
         am_[t] = am;
         a_n[t] = a_oh[t] = a_ow[t] = 0;
         if (am < M) {
-            a_n[t] = am / (s.OH * s.OW);
-            int rem = am % (s.OH * s.OW);
-            a_oh[t] = rem / s.OW;
-            a_ow[t] = rem % s.OW;
+            if constexpr (POOL) {
+                pool_row_decode(am, PH, PW, a_n[t], a_oh[t], a_ow[t]);
+            } else {
+                a_n[t] = am / (s.OH * s.OW);
+                int rem = am % (s.OH * s.OW);
+                a_oh[t] = rem / s.OW;
+                a_ow[t] = rem % s.OW;
+            }
         }
     }
 
@@ -420,6 +478,15 @@ conv_fwd_kernel(const unsigned short* __restrict__ x,
         const int col = n0 + wn * FN * 16 + j * 16 + (lane & 15);
         if (col >= s.Kout) continue;
         const float bv = bias ? bias[col] : 0.f;
+        if constexpr (POOL) {
+#pragma unroll
+            for (int i = 0; i < FM; ++i) {
+                const int row = m0 + wm * FM * 16 + i * 16 + (lane >> 4) * 4;
+                if (row >= M) continue;  // M % 4 == 0: whole window in or out
+                pool_epilogue_store(acc[i][j], bv, y, pidx,
+                                    (int64_t)(row >> 2) * s.Kout + col);
+            }
+        } else {
 #pragma unroll
         for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -430,6 +497,7 @@ conv_fwd_kernel(const unsigned short* __restrict__ x,
                 if (relu) v = v > 0.f ? v : 0.f;
                 y[(int64_t)row * s.Kout + col] = f2bf(v);
             }
+        }
     }
 }
 
@@ -461,15 +529,20 @@ __device__ __forceinline__ void glds16(const unsigned short* src, void* lds_base
                                      0, 0);
 }
 
-template <int BM, int BN, int WM, int WN, int FM, int FN, int BK = 32>
+// POOL = true: window-major rows + pooled epilogue as in conv_fwd_kernel
+// (single k-chunk only; y = pooled output, pidx = argmax). ----
+template <int BM, int BN, int WM, int WN, int FM, int FN, int BK = 32,
+          bool POOL = false>
 __global__ void __launch_bounds__(TPB)
 conv_fwd_glds_kernel(const unsigned short* __restrict__ x,
                      const unsigned short* __restrict__ w,
                      const float* __restrict__ bias,
                      unsigned short* __restrict__ y,
                      float* __restrict__ y32,  // split-K accumulator (or null)
+                     uint8_t* __restrict__ pidx,
                      const unsigned short* __restrict__ zbuf, ConvShape s,
                      int relu, int k_chunks) {
+    static_assert(!POOL || (BM % 4 == 0), "pool windows must not straddle tiles");
     // ONE shared object (two makes hipcc emit a vmcnt(0) drain before each
     // k-step's first ds_read, defeating the glds pipeline — guide trap 4a)
     __shared__ unsigned short smem[3 * (BM + BN) * BK];
@@ -487,7 +560,8 @@ conv_fwd_glds_kernel(const unsigned short* __restrict__ x,
     const int lane = tid & 63;
     const int m0 = xcd_remap(blockIdx.x, gridDim.x) * BM;
     const int n0 = blockIdx.y * BN;
-    const int M = s.N * s.OH * s.OW;
+    const int PH = s.OH >> 1, PW = s.OW >> 1;  // POOL only
+    const int M = POOL ? s.N * PH * PW * 4 : s.N * s.OH * s.OW;
     const int KK = s.R * s.S * s.C;
 
     constexpr int CPR = BK / 8;  // chunks per row
@@ -508,10 +582,14 @@ conv_fwd_glds_kernel(const unsigned short* __restrict__ x,
         a_ok[t] = am < M;
         a_n[t] = a_oh[t] = a_ow[t] = 0;
         if (a_ok[t]) {
-            a_n[t] = am / (s.OH * s.OW);
-            int rem = am % (s.OH * s.OW);
-            a_oh[t] = rem / s.OW;
-            a_ow[t] = rem % s.OW;
+            if constexpr (POOL) {
+                pool_row_decode(am, PH, PW, a_n[t], a_oh[t], a_ow[t]);
+            } else {
+                a_n[t] = am / (s.OH * s.OW);
+                int rem = am % (s.OH * s.OW);
+                a_oh[t] = rem / s.OW;
+                a_ow[t] = rem % s.OW;
+            }
         }
     }
 
@@ -605,6 +683,15 @@ conv_fwd_glds_kernel(const unsigned short* __restrict__ x,
         const int col = n0 + wn * FN * 16 + j * 16 + (lane & 15);
         if (col >= s.Kout) continue;
         const float bv = bias ? bias[col] : 0.f;
+        if constexpr (POOL) {
+#pragma unroll
+            for (int i = 0; i < FM; ++i) {
+                const int row = m0 + wm * FM * 16 + i * 16 + (lane >> 4) * 4;
+                if (row >= M) continue;  // M % 4 == 0: whole window in or out
+                pool_epilogue_store(acc[i][j], bv, y, pidx,
+                                    (int64_t)(row >> 2) * s.Kout + col);
+            }
+        } else {
 #pragma unroll
         for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -619,6 +706,7 @@ conv_fwd_glds_kernel(const unsigned short* __restrict__ x,
                     y[(int64_t)row * s.Kout + col] = f2bf(v);
                 }
             }
+        }
     }
 }
 
@@ -3969,16 +4057,19 @@ float* acc_pool(int64_t n, const torch::TensorOptions& opts,
 // Host wrappers
 // ---------------------------------------------------------------------------
 
-torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,
-                         int64_t stride, bool relu, int64_t pad) {
-    CHECK_GPU(x);
-    TORCH_CHECK(x.is_contiguous() && w.is_contiguous());
-    TORCH_CHECK(x.dtype() == torch::kBFloat16 && w.dtype() == torch::kBFloat16);
-    ConvShape s = make_shape(x, w, (int)stride, (int)pad);
-    auto y = torch::empty({s.N, s.OH, s.OW, s.Kout}, x.options());
+// Which forward kernel a conv shape runs on. The predicates live here and
+// nowhere else: conv2d_fwd launches what the plan says, and
+// conv2d_relu_pool_fwd fuses the pool exactly where the plan names a kernel
+// that has a POOL instantiation, so the two entry points cannot drift apart.
+struct ConvFwdPlan {
+    enum Kind { TILE3, GLDS64, GLDS32, GATHER64, GATHER16 } kind;
+    int k_chunks = 1;     // GLDS64 / GLDS32: split-K factor (grid.z)
+    int TH = 0, BN3 = 0;  // TILE3: tile height and column-tile width
+};
+
+static ConvFwdPlan conv_fwd_plan(const ConvShape& s) {
+    ConvFwdPlan p;
     const int M = s.N * s.OH * s.OW;
-    const float* bias = b.numel() ? b.data_ptr<float>() : nullptr;
-    auto stream = at::cuda::getCurrentCUDAStream();
     const int KKf = s.R * s.S * s.C;
     // Direct tiled kernel for 3x3 s1 convs with C % 32 == 0: the input
     // tile is staged once per channel slab and all nine taps compute from
@@ -4006,20 +4097,10 @@ torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,
         if (s.OH >= 12 && tiles(16, 16) >= min_tiles) TH = 16;
         else if (t3mode >= 2 && s.OH >= 6 && tiles(8, 16) >= min_tiles) TH = 8;
         if (TH) {
-            const int th_ = ceildiv(s.OH, TH), tw_ = ceildiv(s.OW, 16);
-            dim3 grid((unsigned)(s.N * th_ * tw_), (unsigned)kt);
-            #define LAUNCH_T3(TH_, TW_, BN_, WM_, WN_, FM_, FN_)              \
-                hipLaunchKernelGGL(                                           \
-                    (conv_fwd_tile3_kernel<TH_, TW_, BN_, WM_, WN_, FM_,      \
-                                           FN_>),                             \
-                    grid, dim3(TPB), 0, stream, bf_ptr(x), bf_ptr(w), bias,   \
-                    bf_ptr_mut(y), s, relu ? 1 : 0, th_, tw_)
-            if (TH == 16 && BN3 == 64)      LAUNCH_T3(16, 16, 64, 2, 2, 8, 2);
-            else if (TH == 16)              LAUNCH_T3(16, 16, 32, 4, 1, 4, 2);
-            else if (BN3 == 64)             LAUNCH_T3(8, 16, 64, 2, 2, 4, 2);
-            else                            LAUNCH_T3(8, 16, 32, 2, 2, 4, 1);
-            #undef LAUNCH_T3
-            return y;
+            p.kind = ConvFwdPlan::TILE3;
+            p.TH = TH;
+            p.BN3 = BN3;
+            return p;
         }
     }
     // Measured on MI355X (profiles/r02_bench_conv_glds64 vs _glds32): the
@@ -4032,17 +4113,67 @@ torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,
         const char* e = getenv("HEFL_GLDS64");
         return e && e[0] == '1';
     }();
-    if (use64 && s.Kout > 16 && s.C % 8 == 0 && KKf % 8 == 0) {
-        static torch::Tensor zbuf64;
-        if (!zbuf64.defined() || zbuf64.device() != x.device())
-            zbuf64 = torch::zeros({8}, x.options());
+    const bool glds_ok = s.Kout > 16 && s.C % 8 == 0 && KKf % 8 == 0;
+    if (use64 && glds_ok) {
+        p.kind = ConvFwdPlan::GLDS64;
         const bool narrow = s.Kout <= 32;  // BN=32 tile: no wasted columns
         const int BM = narrow ? 256 : 128, BN = narrow ? 32 : 64;
-        int tiles = ceildiv(M, BM) * ceildiv(s.Kout, BN);
-        int ksteps = ceildiv(KKf, 64);
-        int k_chunks = 1;
+        const int tiles = ceildiv(M, BM) * ceildiv(s.Kout, BN);
+        const int ksteps = ceildiv(KKf, 64);
         if (tiles < 256 && ksteps >= 8)
-            k_chunks = std::max(1, std::min(ksteps / 2, 512 / std::max(tiles, 1)));
+            p.k_chunks = std::max(1, std::min(ksteps / 2, 512 / std::max(tiles, 1)));
+    } else if (glds_ok) {
+        // small-M/N late layers split the K loop over grid.z to fill the chip
+        p.kind = ConvFwdPlan::GLDS32;
+        const int tiles = ceildiv(M, 64) * ceildiv(s.Kout, 64);
+        const int ksteps = ceildiv(KKf, 32);
+        if (tiles < 256 && ksteps >= 16)
+            p.k_chunks = std::max(1, std::min(ksteps / 4, 512 / tiles));
+    } else {
+        p.kind = s.Kout > 16 ? ConvFwdPlan::GATHER64 : ConvFwdPlan::GATHER16;
+    }
+    return p;
+}
+
+// 16-B zero scratch the glds kernels DMA from for out-of-range lanes.
+static const unsigned short* conv_zbuf(const torch::Tensor& x) {
+    static torch::Tensor zbuf;
+    if (!zbuf.defined() || zbuf.device() != x.device())
+        zbuf = torch::zeros({8}, x.options());
+    return bf_ptr(zbuf);
+}
+
+torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,
+                         int64_t stride, bool relu, int64_t pad) {
+    CHECK_GPU(x);
+    TORCH_CHECK(x.is_contiguous() && w.is_contiguous());
+    TORCH_CHECK(x.dtype() == torch::kBFloat16 && w.dtype() == torch::kBFloat16);
+    ConvShape s = make_shape(x, w, (int)stride, (int)pad);
+    auto y = torch::empty({s.N, s.OH, s.OW, s.Kout}, x.options());
+    const int M = s.N * s.OH * s.OW;
+    const float* bias = b.numel() ? b.data_ptr<float>() : nullptr;
+    auto stream = at::cuda::getCurrentCUDAStream();
+    const ConvFwdPlan plan = conv_fwd_plan(s);
+    const int k_chunks = plan.k_chunks;
+    if (plan.kind == ConvFwdPlan::TILE3) {
+        const int TH = plan.TH, BN3 = plan.BN3;
+        const int kt = ceildiv(s.Kout, BN3);
+        const int th_ = ceildiv(s.OH, TH), tw_ = ceildiv(s.OW, 16);
+        dim3 grid((unsigned)(s.N * th_ * tw_), (unsigned)kt);
+        #define LAUNCH_T3(TH_, TW_, BN_, WM_, WN_, FM_, FN_)                  \
+            hipLaunchKernelGGL(                                               \
+                (conv_fwd_tile3_kernel<TH_, TW_, BN_, WM_, WN_, FM_, FN_>),   \
+                grid, dim3(TPB), 0, stream, bf_ptr(x), bf_ptr(w), bias,       \
+                bf_ptr_mut(y), s, relu ? 1 : 0, th_, tw_)
+        if (TH == 16 && BN3 == 64)      LAUNCH_T3(16, 16, 64, 2, 2, 8, 2);
+        else if (TH == 16)              LAUNCH_T3(16, 16, 32, 4, 1, 4, 2);
+        else if (BN3 == 64)             LAUNCH_T3(8, 16, 64, 2, 2, 4, 2);
+        else                            LAUNCH_T3(8, 16, 32, 2, 2, 4, 1);
+        #undef LAUNCH_T3
+    } else if (plan.kind == ConvFwdPlan::GLDS64) {
+        const bool narrow = s.Kout <= 32;  // BN=32 tile: no wasted columns
+        const int BM = narrow ? 256 : 128, BN = narrow ? 32 : 64;
+        const unsigned short* zbuf = conv_zbuf(x);
         dim3 grid(ceildiv(M, BM), ceildiv(s.Kout, BN), k_chunks);
         torch::Tensor y32;
         float* y32p = nullptr;
@@ -4053,7 +4184,7 @@ torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,
                                                        FM_, FN_, P0>),       \
                                grid, dim3(TPB), 0, stream, bf_ptr(x),         \
                                bf_ptr(w), bias, bf_ptr_mut(y), y32p,          \
-                               bf_ptr(zbuf64), s, relu ? 1 : 0, k_chunks)
+                               zbuf, s, relu ? 1 : 0, k_chunks)
         if (narrow) {
             if (s.pad == 0) LAUNCH_F64(256, 32, 4, 1, 4, 2, true);
             else            LAUNCH_F64(256, 32, 4, 1, 4, 2, false);
@@ -4069,19 +4200,9 @@ torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,
                                dim3(256), 0, stream, y32p, bias,
                                bf_ptr_mut(y), total, s.Kout, relu ? 1 : 0, 1, 1);
         }
-        return y;
-    }
-    if (s.Kout > 16 && s.C % 8 == 0 && KKf % 8 == 0) {
-        // glds double-buffered pipeline (DMA flight hides under MFMA);
-        // small-M/N late layers split the K loop over grid.z to fill the chip
-        static torch::Tensor zbuf;
-        if (!zbuf.defined() || zbuf.device() != x.device())
-            zbuf = torch::zeros({8}, x.options());
-        int tiles = ceildiv(M, 64) * ceildiv(s.Kout, 64);
-        int ksteps = ceildiv(KKf, 32);
-        int k_chunks = 1;
-        if (tiles < 256 && ksteps >= 16)
-            k_chunks = std::max(1, std::min(ksteps / 4, 512 / tiles));
+    } else if (plan.kind == ConvFwdPlan::GLDS32) {
+        // glds three-buffer pipeline (DMA flight hides under MFMA)
+        const unsigned short* zbuf = conv_zbuf(x);
         dim3 grid(ceildiv(M, 64), ceildiv(s.Kout, 64), k_chunks);
         if (k_chunks > 1) {
             torch::Tensor y32h;
@@ -4089,8 +4210,8 @@ torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,
                                    y32h);
             hipLaunchKernelGGL((conv_fwd_glds_kernel<64, 64, 2, 2, 2, 2, 32>),
                                grid, dim3(TPB), 0, stream, bf_ptr(x), bf_ptr(w),
-                               bias, bf_ptr_mut(y), y32p,
-                               bf_ptr(zbuf), s, relu ? 1 : 0, k_chunks);
+                               bias, bf_ptr_mut(y), y32p, (uint8_t*)nullptr,
+                               zbuf, s, relu ? 1 : 0, k_chunks);
             int64_t total = (int64_t)M * s.Kout;
             hipLaunchKernelGGL(linear_epilogue_kernel,
                                dim3((int)std::min<int64_t>(ceildiv(total, 256), 2048)),
@@ -4100,20 +4221,75 @@ torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,
             hipLaunchKernelGGL((conv_fwd_glds_kernel<64, 64, 2, 2, 2, 2, 32>),
                                grid, dim3(TPB), 0, stream, bf_ptr(x), bf_ptr(w),
                                bias, bf_ptr_mut(y), (float*)nullptr,
-                               bf_ptr(zbuf), s, relu ? 1 : 0, 1);
+                               (uint8_t*)nullptr, zbuf, s, relu ? 1 : 0, 1);
         }
-    } else if (s.Kout > 16) {
+    } else if (plan.kind == ConvFwdPlan::GATHER64) {
         dim3 grid(ceildiv(M, 64), ceildiv(s.Kout, 64));
         hipLaunchKernelGGL((conv_fwd_kernel<64, 64, 2, 2, 2, 2>), grid,
                            dim3(TPB), 0, stream, bf_ptr(x), bf_ptr(w), bias,
-                           bf_ptr_mut(y), s, relu ? 1 : 0);
+                           bf_ptr_mut(y), (uint8_t*)nullptr, s, relu ? 1 : 0);
     } else {
         dim3 grid(ceildiv(M, 64), ceildiv(s.Kout, 16));
         hipLaunchKernelGGL((conv_fwd_kernel<64, 16, 4, 1, 1, 1>), grid,
                            dim3(TPB), 0, stream, bf_ptr(x), bf_ptr(w), bias,
-                           bf_ptr_mut(y), s, relu ? 1 : 0);
+                           bf_ptr_mut(y), (uint8_t*)nullptr, s, relu ? 1 : 0);
     }
     return y;
+}
+
+std::vector<torch::Tensor> maxpool2x2_fwd(torch::Tensor x);
+
+// conv(+bias+ReLU, stride 1) -> maxpool2x2 in ONE launch wherever the conv
+// runs on an implicit-GEMM kernel with a POOL instantiation (generic gather
+// or the single-k-chunk BK=32 glds pipeline): the pre-pool activation is
+// never allocated, written or read back. Every other dispatch (direct tiled
+// kernel, HEFL_GLDS64 probe, split-K, empty pooled output) runs the composed
+// conv2d_fwd + maxpool2x2_fwd pair unchanged. Returns {p, idx, OH, OW} with
+// p/idx exactly what maxpool2x2_fwd returns and OH/OW the conv output size
+// (what pool_relu_bias_bwd needs).
+std::tuple<torch::Tensor, torch::Tensor, int64_t, int64_t>
+conv2d_relu_pool_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,
+                     int64_t pad) {
+    CHECK_GPU(x);
+    TORCH_CHECK(x.is_contiguous() && w.is_contiguous());
+    TORCH_CHECK(x.dtype() == torch::kBFloat16 && w.dtype() == torch::kBFloat16);
+    ConvShape s = make_shape(x, w, 1, (int)pad);
+    const int PH = s.OH / 2, PW = s.OW / 2;
+    const ConvFwdPlan plan = conv_fwd_plan(s);
+    const bool fuse =
+        PH > 0 && PW > 0 &&
+        (plan.kind == ConvFwdPlan::GATHER16 ||
+         plan.kind == ConvFwdPlan::GATHER64 ||
+         (plan.kind == ConvFwdPlan::GLDS32 && plan.k_chunks == 1));
+    if (!fuse) {
+        auto y = conv2d_fwd(x, w, b, 1, true, pad);
+        auto pi = maxpool2x2_fwd(y);
+        return {pi[0], pi[1], (int64_t)s.OH, (int64_t)s.OW};
+    }
+    auto p = torch::empty({s.N, PH, PW, s.Kout}, x.options());
+    auto idx = torch::empty({s.N, PH, PW, s.Kout},
+                            x.options().dtype(torch::kUInt8));
+    const int M = s.N * PH * PW * 4;  // window-major rows, 4 cells per window
+    const float* bias = b.numel() ? b.data_ptr<float>() : nullptr;
+    auto stream = at::cuda::getCurrentCUDAStream();
+    if (plan.kind == ConvFwdPlan::GLDS32) {
+        dim3 grid(ceildiv(M, 64), ceildiv(s.Kout, 64), 1);
+        hipLaunchKernelGGL(
+            (conv_fwd_glds_kernel<64, 64, 2, 2, 2, 2, 32, true>), grid,
+            dim3(TPB), 0, stream, bf_ptr(x), bf_ptr(w), bias, bf_ptr_mut(p),
+            (float*)nullptr, idx.data_ptr<uint8_t>(), conv_zbuf(x), s, 1, 1);
+    } else if (plan.kind == ConvFwdPlan::GATHER64) {
+        dim3 grid(ceildiv(M, 64), ceildiv(s.Kout, 64));
+        hipLaunchKernelGGL((conv_fwd_kernel<64, 64, 2, 2, 2, 2, true>), grid,
+                           dim3(TPB), 0, stream, bf_ptr(x), bf_ptr(w), bias,
+                           bf_ptr_mut(p), idx.data_ptr<uint8_t>(), s, 1);
+    } else {
+        dim3 grid(ceildiv(M, 64), ceildiv(s.Kout, 16));
+        hipLaunchKernelGGL((conv_fwd_kernel<64, 16, 4, 1, 1, 1, true>), grid,
+                           dim3(TPB), 0, stream, bf_ptr(x), bf_ptr(w), bias,
+                           bf_ptr_mut(p), idx.data_ptr<uint8_t>(), s, 1);
+    }
+    return {p, idx, (int64_t)s.OH, (int64_t)s.OW};
 }
 
 torch::Tensor conv2d_dgrad(torch::Tensor dy, torch::Tensor w, int64_t stride,

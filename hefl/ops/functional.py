@@ -81,6 +81,12 @@ _HEAD_XENT = os.getenv("HEFL_HEAD_XENT", "1") != "0"
 # launches): dgrad and wgrad of a Dense layer in ONE launch (blockIdx.z
 # selects the role; bit-identical outputs).
 _LIN_PAIR = os.getenv("HEFL_LIN_PAIR", "1") != "0"
+# Pool fused into the conv forward epilogue (default ON, HEFL_CONV_POOL=0
+# restores conv2d_fwd + maxpool2x2_fwd): conv2d_relu_pool_fwd enumerates
+# the implicit-GEMM rows pool-window-major so the 2x2 max is three register
+# compares in the epilogue; the pre-pool activation is never written.
+# Bit-identical p / idx (tests/test_gpu_conv_pool_fused.py).
+_CONV_POOL = os.getenv("HEFL_CONV_POOL", "1") != "0"
 
 # Epoch-graph capture contract (fl/client.py sets this around warmup +
 # capture; HEFL_GRAPH_NO_ZERO=0 disables): while True, conv dw / bias db
@@ -247,10 +253,13 @@ def maxpool2x2(x):
 class _ConvReluPoolFn(torch.autograd.Function):
     """Fused conv(+bias+ReLU) -> maxpool2x2 trunk block (GPU only).
 
-    Forward launches the same two kernels as the composed ops; the win is in
-    backward: ONE pool_relu_bias_bwd kernel produces the gated conv-activation
-    gradient AND the bias gradient (replacing maxpool2x2_bwd + relu_bias_bwd,
-    i.e. two full passes over the activation-gradient tensor)."""
+    Forward is ONE launch where the conv runs on an implicit-GEMM kernel
+    (conv2d_relu_pool_fwd pools in the conv epilogue and never materialises
+    the pre-pool activation); other dispatches, and HEFL_CONV_POOL=0, run
+    conv2d_fwd + maxpool2x2_fwd with identical results. Backward: ONE
+    pool_relu_bias_bwd kernel produces the gated conv-activation gradient
+    AND the bias gradient (replacing maxpool2x2_bwd + relu_bias_bwd, i.e.
+    two full passes over the activation-gradient tensor)."""
 
     @staticmethod
     def forward(ctx, x, w, b, pad: int):
@@ -264,9 +273,15 @@ class _ConvReluPoolFn(torch.autograd.Function):
             x = _pad8(x)
             wb = _pad8(wb)
         bb = b.detach().float()
-        y = _C().conv2d_fwd(x.contiguous(), wb.contiguous(), bb, 1, True, pad)
-        ctx.conv_hw = (y.shape[1], y.shape[2])
-        p, idx = _C().maxpool2x2_fwd(y)
+        if _CONV_POOL:
+            p, idx, ch, cw = _C().conv2d_relu_pool_fwd(
+                x.contiguous(), wb.contiguous(), bb, pad)
+            ctx.conv_hw = (ch, cw)
+        else:
+            y = _C().conv2d_fwd(x.contiguous(), wb.contiguous(), bb, 1, True,
+                                pad)
+            ctx.conv_hw = (y.shape[1], y.shape[2])
+            p, idx = _C().maxpool2x2_fwd(y)
         # backward gates on the POOLED output p (= y at the argmax; relu ran
         # before pool) — the full pre-pool activation y is not retained
         ctx.save_for_backward(x, wb, p, idx)
