@@ -48,6 +48,19 @@ def main():
                          "and RESUME from PATH if it exists — the round-"
                          "granularity recovery the reference gets only "
                          "implicitly from its pickle files (SURVEY.md §5)")
+    ap.add_argument("--data-dir", default=None, metavar="DIR",
+                    help="train on the images under DIR/<class>/* (PNG, "
+                         "PGM/PPM, BMP, .npy; others through Pillow when "
+                         "installed) instead of synthetic data; the class "
+                         "count is taken from the folder")
+    ap.add_argument("--test-dir", default=None, metavar="DIR",
+                    help="held-out DIR/<class>/* folder the aggregated model "
+                         "is evaluated on (required with --data-dir in "
+                         "single-process mode)")
+    ap.add_argument("--in-shape", type=int, nargs=3, default=None,
+                    metavar=("H", "W", "C"),
+                    help="override the preset's input shape (images are "
+                         "resized to it)")
     ap.add_argument("--json", action="store_true", help="JSON line output")
     args = ap.parse_args()
 
@@ -55,6 +68,24 @@ def main():
     from hefl.parallel.dist import get_rank, get_world_size, init_distributed
 
     cfg = preset(args.preset)
+    if args.in_shape is not None:
+        cfg.model.in_shape = tuple(args.in_shape)
+    if args.test_dir and not args.data_dir:
+        ap.error("--test-dir needs --data-dir")
+    if args.data_dir:
+        import os
+        if not os.path.isdir(args.data_dir):
+            ap.error(f"--data-dir {args.data_dir}: no such directory")
+        single = int(os.environ.get("WORLD_SIZE", "1")) <= 1
+        if single and not args.test_dir:
+            ap.error("--data-dir needs --test-dir: the aggregated model is "
+                     "evaluated on a held-out folder, never on training data")
+        classes = [d for d in sorted(os.listdir(args.data_dir))
+                   if os.path.isdir(os.path.join(args.data_dir, d))]
+        if not classes:
+            ap.error(f"--data-dir {args.data_dir}: no <class>/ sub-folders")
+        cfg.fl.data_dir, cfg.fl.test_dir = args.data_dir, args.test_dir
+        cfg.model.n_classes = len(classes)
     if args.clients:
         cfg.fl.n_clients = args.clients
     if args.plaintext:

@@ -82,6 +82,11 @@ class FLConfig:
     # secret key (hefl/fl/secure.py)
     key_mode: str = "shared"
     smudge_bits: int = 16                 # threshold decryption smudging noise width
+    # Real data: `data_dir/<class>/*` image folder the clients shard (the
+    # reference's prep_df + flow_from_dataframe input, FLPyfhelin.py:38-114)
+    # and the held-out `test_dir/<class>/*`. Unset -> synthetic data.
+    data_dir: Optional[str] = None
+    test_dir: Optional[str] = None
 
 
 @dataclass

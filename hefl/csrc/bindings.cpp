@@ -78,6 +78,13 @@ torch::Tensor synth_batch(torch::Tensor templates, torch::Tensor labels,
 torch::Tensor synth_batch_g(torch::Tensor templates, torch::Tensor labels,
                             torch::Tensor seed_buf, int64_t salt, double zoom,
                             double shear, int64_t flip);
+torch::Tensor image_batch(torch::Tensor store, torch::Tensor idx, int64_t seed,
+                          int64_t H, int64_t W, double zoom, double shear,
+                          int64_t flip);
+torch::Tensor image_batch_g(torch::Tensor store, torch::Tensor idx,
+                            torch::Tensor seed_buf, int64_t salt, int64_t H,
+                            int64_t W, double zoom, double shear,
+                            int64_t flip);
 torch::Tensor maxpool2x2_bwd(torch::Tensor dy, torch::Tensor idx, int64_t H,
                              int64_t W);
 std::vector<torch::Tensor> softmax_xent_fwd(torch::Tensor logits,
@@ -197,6 +204,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("flip") = 0);
     m.def("synth_batch_g", &synth_batch_g, py::arg("templates"),
           py::arg("labels"), py::arg("seed_buf"), py::arg("salt"),
+          py::arg("zoom") = 0.0, py::arg("shear") = 0.0, py::arg("flip") = 0);
+    m.def("image_batch", &image_batch, py::arg("store"), py::arg("idx"),
+          py::arg("seed"), py::arg("H"), py::arg("W"), py::arg("zoom") = 0.0,
+          py::arg("shear") = 0.0, py::arg("flip") = 0);
+    m.def("image_batch_g", &image_batch_g, py::arg("store"), py::arg("idx"),
+          py::arg("seed_buf"), py::arg("salt"), py::arg("H"), py::arg("W"),
           py::arg("zoom") = 0.0, py::arg("shear") = 0.0, py::arg("flip") = 0);
     m.def("maxpool2x2_bwd", &maxpool2x2_bwd);
     m.def("softmax_xent_fwd", &softmax_xent_fwd);

@@ -65,6 +65,11 @@
 //   synth_batch_kernel<AUG>        one-pass synthetic data generation,
 //                                  AUG = in-kernel zoom/shear/flip via
 //                                  inverse-affine template sampling
+//   image_batch_kernel<C>          real-image staging from a uint8 store:
+//                                  gather + resize + zoom/shear/flip +
+//                                  1/255 + bf16 in one pass;
+//                                  image_gather_vec/px_kernel = its
+//                                  no-resize/no-augment fast paths
 //   head_xent_fwd/bwd_kernel       classifier tail (last Dense + softmax-CE
 //                                  and their backward) in two single-
 //                                  workgroup launches
@@ -2004,6 +2009,130 @@ __global__ void synth_batch_kernel(const float* __restrict__ T,
         const float nrm = sqrtf(-2.f * __logf(u1)) * __cosf(6.2831853f * u2);
         const float v = 0.6f * t + 0.4f * nrm;
         out[i] = f2bf(1.f / (1.f + __expf(-v)));  // sigmoid -> [0,1]
+    }
+}
+
+// Real-image staging: gather samples idx[j] from a resident uint8 store
+// [N,Hs,Ws,C], resize to HxW and apply the same per-sample zoom/shear/h-flip
+// as synth_batch_kernel<true> (same hash chain, keyed on the OUTPUT position
+// j), rescale by 1/255 and store bf16 — decode-free replacement for the
+// reference's flow_from_dataframe + ImageDataGenerator pass
+// (FLPyfhelin.py:57-114), capturable into the epoch graph. Stored indices
+// are clamped to [0, N) so a bad index can never read outside the store
+// (the dataset rejects them on the host first).
+__device__ __forceinline__ int64_t image_src(const int64_t* __restrict__ idx,
+                                             unsigned j, int64_t n_store) {
+    const int64_t s = idx[j];
+    return s < 0 ? 0 : (s >= n_store ? n_store - 1 : s);
+}
+
+// Fast path (no resize, no augmentation, 16 | bytes per image): one lane
+// moves 16 source bytes with one 16-B load and two 16-B bf16 stores.
+__global__ void image_gather_vec_kernel(const uint4* __restrict__ store,
+                                        const int64_t* __restrict__ idx,
+                                        uint4* __restrict__ out,
+                                        int64_t n_store, unsigned per16,
+                                        unsigned total16, FastDiv fPer16) {
+    for (unsigned q = blockIdx.x * blockDim.x + threadIdx.x; q < total16;
+         q += gridDim.x * blockDim.x) {
+        const unsigned j = fdiv(q, fPer16);
+        const unsigned off = q - j * per16;
+        const uint4 v = store[image_src(idx, j, n_store) * per16 + off];
+        const unsigned wds[4] = {v.x, v.y, v.z, v.w};
+        unsigned o[8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned b = wds[k];
+            const unsigned b0 = f2bf((float)(b & 0xffu) * (1.0f / 255.0f));
+            const unsigned b1 = f2bf((float)((b >> 8) & 0xffu) * (1.0f / 255.0f));
+            const unsigned b2 = f2bf((float)((b >> 16) & 0xffu) * (1.0f / 255.0f));
+            const unsigned b3 = f2bf((float)(b >> 24) * (1.0f / 255.0f));
+            o[2 * k] = b0 | (b1 << 16);
+            o[2 * k + 1] = b2 | (b3 << 16);
+        }
+        out[2 * (int64_t)q] = make_uint4(o[0], o[1], o[2], o[3]);
+        out[2 * (int64_t)q + 1] = make_uint4(o[4], o[5], o[6], o[7]);
+    }
+}
+
+// Fast-path fallback for image sizes that are no multiple of 16 bytes: one
+// lane per pixel, scalar bytes.
+template <int C>
+__global__ void image_gather_px_kernel(const uint8_t* __restrict__ store,
+                                       const int64_t* __restrict__ idx,
+                                       unsigned short* __restrict__ out,
+                                       int64_t n_store, unsigned HW,
+                                       unsigned total_px, FastDiv fHW) {
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total_px;
+         i += gridDim.x * blockDim.x) {
+        const unsigned j = fdiv(i, fHW);
+        const unsigned hw = i - j * HW;
+        const uint8_t* src =
+            store + (image_src(idx, j, n_store) * HW + hw) * C;
+        unsigned short* dst = out + (int64_t)i * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            dst[c] = f2bf((float)src[c] * (1.0f / 255.0f));
+    }
+}
+
+// General path: one lane = one output pixel, all C channels; consecutive
+// lanes take consecutive w, so the two source rows and the output row are
+// read/written contiguously. ry/rx = (Hs-1)/(H-1), (Ws-1)/(W-1) (0 for a
+// degenerate target extent): the align_corners=True target->source scale.
+template <int C>
+__global__ void image_batch_kernel(const uint8_t* __restrict__ store,
+                                   const int64_t* __restrict__ idx,
+                                   unsigned short* __restrict__ out,
+                                   int64_t n_store, unsigned total_px,
+                                   unsigned long long seed,
+                                   const long long* __restrict__ seed_buf,
+                                   int Hs, int Ws, int H, int W, FastDiv fHW,
+                                   FastDiv fW, float ry, float rx, float zr,
+                                   float sr, int flip) {
+    if (seed_buf) seed += (unsigned long long)seed_buf[0];  // graph-replay seed
+    const unsigned HW = (unsigned)H * (unsigned)W;
+    const float cy = 0.5f * (H - 1), cx = 0.5f * (W - 1);
+    unsigned cur = 0xffffffffu;  // sample whose parameters are cached
+    float zoom = 1.f, shear = 0.f, sf = 1.f;
+    const uint8_t* S = store;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total_px;
+         i += gridDim.x * blockDim.x) {
+        const unsigned j = fdiv(i, fHW);
+        const unsigned hw = i - j * HW;
+        const unsigned hh = fdiv(hw, fW);
+        const int w = (int)(hw - hh * W);
+        const int h = (int)hh;
+        if (j != cur) {  // per-SAMPLE hash chain, once per lane and sample
+            cur = j;
+            const unsigned long long pz =
+                splitmix64(seed ^ (0xA5A5A5A5ull + (unsigned long long)j));
+            const float uz = (unsigned int)pz * 2.3283064e-10f;
+            const float us = (unsigned int)(pz >> 32) * 2.3283064e-10f;
+            const float uf = (unsigned int)splitmix64(pz) * 2.3283064e-10f;
+            zoom = 1.f + zr * (2.f * uz - 1.f);
+            shear = sr * (2.f * us - 1.f);
+            sf = (flip && uf < 0.5f) ? -1.f : 1.f;
+            S = store + image_src(idx, j, n_store) * ((int64_t)Hs * Ws * C);
+        }
+        const float ty = cy + (h - cy) / zoom;
+        const float tx = cx + (w - cx) * sf / zoom + shear * (h - cy);
+        const float syc = fminf(fmaxf(ty * ry, 0.f), (float)(Hs - 1));
+        const float sxc = fminf(fmaxf(tx * rx, 0.f), (float)(Ws - 1));
+        const int y0 = (int)syc, x0 = (int)sxc;
+        const int y1 = min(y0 + 1, Hs - 1), x1 = min(x0 + 1, Ws - 1);
+        const float fy = syc - y0, fx = sxc - x0;
+        const uint8_t* r0 = S + (int64_t)y0 * Ws * C;
+        const uint8_t* r1 = S + (int64_t)y1 * Ws * C;
+        unsigned short* dst = out + (int64_t)i * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float t00 = r0[x0 * C + c], t01 = r0[x1 * C + c];
+            const float t10 = r1[x0 * C + c], t11 = r1[x1 * C + c];
+            const float t = (t00 * (1 - fx) + t01 * fx) * (1 - fy)
+                            + (t10 * (1 - fx) + t11 * fx) * fy;
+            dst[c] = f2bf(t * (1.0f / 255.0f));
+        }
     }
 }
 
@@ -4754,6 +4883,97 @@ torch::Tensor synth_batch_g(torch::Tensor templates, torch::Tensor labels,
     return synth_launch(templates, labels, salt,
                         (const long long*)seed_buf.data_ptr<int64_t>(), zoom,
                         shear, flip);
+}
+
+static torch::Tensor image_launch(torch::Tensor store, torch::Tensor idx,
+                                  int64_t seed, const long long* seed_buf,
+                                  int64_t H, int64_t W, double zoom,
+                                  double shear, int64_t flip) {
+    CHECK_GPU(store);
+    CHECK_GPU(idx);
+    TORCH_CHECK(store.scalar_type() == torch::kUInt8 && store.dim() == 4 &&
+                    store.is_contiguous(),
+                "store must be a contiguous uint8 [N,Hs,Ws,C] tensor");
+    TORCH_CHECK(idx.scalar_type() == torch::kInt64 && idx.dim() == 1 &&
+                    idx.is_contiguous(),
+                "idx must be a contiguous int64 [n] tensor");
+    const int64_t N = store.size(0), Hs = store.size(1), Ws = store.size(2),
+                  C = store.size(3), n = idx.size(0);
+    TORCH_CHECK(C == 1 || C == 3 || C == 4, "C must be 1, 3 or 4, got ", C);
+    TORCH_CHECK(N > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0,
+                "empty store or target shape");
+    // 32-bit index decode (like synth_batch_kernel); FastDiv is exact for
+    // dividends below 2^31, which the decoded pixel index must respect
+    TORCH_CHECK(n * H * W * C < (int64_t(1) << 32) &&
+                    n * H * W < (int64_t(1) << 31) &&
+                    Hs * Ws * C < (int64_t(1) << 31),
+                "image_batch: n*H*W*C must be below 2^32");
+    auto out = torch::empty({n, H, W, C},
+                            store.options().dtype(torch::kBFloat16));
+    if (n == 0) return out;
+    auto stream = at::cuda::getCurrentCUDAStream();
+    const uint8_t* sp = store.data_ptr<uint8_t>();
+    const int64_t* ip = idx.data_ptr<int64_t>();
+    unsigned short* op = reinterpret_cast<unsigned short*>(out.data_ptr());
+    const unsigned total_px = (unsigned)(n * H * W);
+    const int blocks = (int)std::min<int64_t>(((int64_t)total_px + 255) / 256,
+                                              8192);
+    const FastDiv fHW = fdiv_make((unsigned)(H * W));
+    const bool plain = zoom == 0.0 && shear == 0.0 && flip == 0 && Hs == H &&
+                       Ws == W;
+    const int64_t per = H * W * C;
+    if (plain && per % 16 == 0 &&
+        reinterpret_cast<uintptr_t>(sp) % 16 == 0 &&
+        reinterpret_cast<uintptr_t>(op) % 16 == 0) {
+        const unsigned per16 = (unsigned)(per / 16);
+        const unsigned total16 = (unsigned)(n * per16);
+        const int vblocks = (int)std::min<int64_t>(
+            ((int64_t)total16 + 255) / 256, 8192);
+        hipLaunchKernelGGL(image_gather_vec_kernel, dim3(vblocks), dim3(256),
+                           0, stream, reinterpret_cast<const uint4*>(sp), ip,
+                           reinterpret_cast<uint4*>(op), N, per16, total16,
+                           fdiv_make(per16));
+        return out;
+    }
+#define IMAGE_LAUNCH_C(CC)                                                    \
+    if (plain)                                                                \
+        hipLaunchKernelGGL(image_gather_px_kernel<CC>, dim3(blocks),          \
+                           dim3(256), 0, stream, sp, ip, op, N,               \
+                           (unsigned)(H * W), total_px, fHW);                 \
+    else                                                                      \
+        hipLaunchKernelGGL(image_batch_kernel<CC>, dim3(blocks), dim3(256),   \
+                           0, stream, sp, ip, op, N, total_px,                \
+                           (unsigned long long)seed, seed_buf, (int)Hs,       \
+                           (int)Ws, (int)H, (int)W, fHW,                      \
+                           fdiv_make((unsigned)W), ry, rx, (float)zoom,       \
+                           (float)shear, (int)flip)
+    const float ry = H > 1 ? (float)(Hs - 1) / (float)(H - 1) : 0.f;
+    const float rx = W > 1 ? (float)(Ws - 1) / (float)(W - 1) : 0.f;
+    if (C == 1) { IMAGE_LAUNCH_C(1); }
+    else if (C == 3) { IMAGE_LAUNCH_C(3); }
+    else { IMAGE_LAUNCH_C(4); }
+#undef IMAGE_LAUNCH_C
+    return out;
+}
+
+torch::Tensor image_batch(torch::Tensor store, torch::Tensor idx, int64_t seed,
+                          int64_t H, int64_t W, double zoom, double shear,
+                          int64_t flip) {
+    return image_launch(store, idx, seed, nullptr, H, W, zoom, shear, flip);
+}
+
+torch::Tensor image_batch_g(torch::Tensor store, torch::Tensor idx,
+                            torch::Tensor seed_buf, int64_t salt, int64_t H,
+                            int64_t W, double zoom, double shear,
+                            int64_t flip) {
+    // graph-capturable variant: base seed read from a device buffer the
+    // host rewrites before each replay (same contract as synth_batch_g)
+    CHECK_GPU(seed_buf);
+    TORCH_CHECK(seed_buf.scalar_type() == torch::kInt64 &&
+                seed_buf.numel() >= 1);
+    return image_launch(store, idx, salt,
+                        (const long long*)seed_buf.data_ptr<int64_t>(), H, W,
+                        zoom, shear, flip);
 }
 
 std::vector<torch::Tensor> maxpool2x2_fwd(torch::Tensor x) {

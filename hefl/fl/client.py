@@ -57,12 +57,34 @@ class LocalClient:
         # FLPyfhelin.py:85-99). Training runs on the train subset only;
         # val metrics feed the callbacks (fit(validation_data=...), :193).
         per_client = cfg.fl.samples_per_client + cfg.fl.val_samples_per_client
-        n_total = cfg.fl.n_clients * per_client
-        self.dataset = SyntheticMedicalImages(
-            n_total, cfg.model.in_shape, cfg.model.n_classes,
-            seed=cfg.fl.seed, device=device, dtype=self.compute_dtype)
-        idx = shard_indices(n_total, client_id, cfg.fl.n_clients)
-        n_val = cfg.fl.val_samples_per_client
+        if cfg.fl.data_dir:
+            # real images: this client decodes and holds only its own
+            # contiguous shard of the (shuffled) folder listing; sample
+            # indices are shard-local. The val split keeps the configured
+            # train:val ratio (10% with defaults = the reference's
+            # validation_split=0.1) whatever the folder's size.
+            from ..data.files import ImageFolderDataset
+            from ..data.shard import prep_df
+            n_listed = len(prep_df(cfg.fl.data_dir, shuffle=False))
+            rows = shard_indices(n_listed, client_id, cfg.fl.n_clients)
+            self.dataset = ImageFolderDataset(
+                cfg.fl.data_dir, cfg.model.in_shape, device=device,
+                dtype=self.compute_dtype, seed=cfg.fl.seed, rows=rows)
+            if self.dataset.n_classes != cfg.model.n_classes:
+                raise ValueError(
+                    f"{cfg.fl.data_dir} has {self.dataset.n_classes} class "
+                    f"folders but the model is configured for "
+                    f"{cfg.model.n_classes} classes")
+            idx = torch.arange(self.dataset.n_samples, dtype=torch.long)
+            n_val = (idx.numel() * cfg.fl.val_samples_per_client
+                     // max(per_client, 1))
+        else:
+            n_total = cfg.fl.n_clients * per_client
+            self.dataset = SyntheticMedicalImages(
+                n_total, cfg.model.in_shape, cfg.model.n_classes,
+                seed=cfg.fl.seed, device=device, dtype=self.compute_dtype)
+            idx = shard_indices(n_total, client_id, cfg.fl.n_clients)
+            n_val = cfg.fl.val_samples_per_client
         train_idx = idx[: idx.numel() - n_val]
         # augmentation applies to TRAINING batches only (the reference's
         # ImageDataGenerator transforms train, not val/test)
@@ -261,7 +283,12 @@ class LocalClient:
         try:
             Fx.GRAPH_NO_ZERO = no_zero
             with torch.cuda.graph(g, stream=side):
-                if in_graph_data:
+                if in_graph_data and hasattr(self.dataset, "graph_batch"):
+                    # folder dataset: its own capturable gather/resize/
+                    # augment kernel over the resident uint8 store
+                    X, Y = self.dataset.graph_batch(order_buf, seed_buf,
+                                                    self.affine)
+                elif in_graph_data:
                     Y = self.dataset.labels.index_select(0, order_buf)
                     zr, sr, fl = self.affine or (0.0, 0.0, False)
                     X = C.synth_batch_g(self.dataset.templates, Y, seed_buf, 0,

@@ -49,6 +49,10 @@ class SequentialFL:
         self.cfg = cfg
         self.device = torch.device(device)
         self.verbose = verbose
+        if cfg.fl.data_dir and not cfg.fl.test_dir:
+            # refusing beats silently reporting metrics on training data
+            raise ValueError("fl.data_dir is set but fl.test_dir is not: a "
+                             "held-out test folder is required to evaluate")
         self.global_model = build_model(cfg.model, seed=cfg.fl.seed).to(self.device)
         self.clients = [LocalClient(cfg, i, device=device)
                         for i in range(cfg.fl.n_clients)]
@@ -74,6 +78,19 @@ class SequentialFL:
         elif cfg.fl.encrypted:
             self.ctx = CKKSContext(cfg.he, device=device)
             self.keys = self.ctx.keygen()
+        if cfg.fl.data_dir:
+            # real images: the held-out folder, every file, unaugmented
+            from ..data.files import ImageFolderDataset
+            self.test_ds = ImageFolderDataset(
+                cfg.fl.test_dir, cfg.model.in_shape, device=device,
+                dtype=self.clients[0].compute_dtype, seed=cfg.fl.seed)
+            if self.test_ds.n_classes != cfg.model.n_classes:
+                raise ValueError(
+                    f"{cfg.fl.test_dir} has {self.test_ds.n_classes} class "
+                    f"folders but the model is configured for "
+                    f"{cfg.model.n_classes} classes")
+            self.test_idx = torch.arange(self.test_ds.n_samples)
+            return
         # held-out test set (reference: 400 test images, notebook cell 0/3):
         # SAME class templates as training (template_seed) so it is the same
         # task, but a disjoint seed for labels/noise — with the raw fl.seed
