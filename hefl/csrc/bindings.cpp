@@ -136,6 +136,12 @@ std::vector<torch::Tensor> dense_head2_bwd(torch::Tensor dlogits,
                                            torch::Tensor w1, torch::Tensor w2);
 std::vector<torch::Tensor> linear_bwd_pair(torch::Tensor dy, torch::Tensor w,
                                            torch::Tensor x);
+bool conv_bwd_pair_ok(torch::Tensor dy, torch::Tensor w, int64_t pad,
+                      int64_t H, int64_t W);
+std::vector<torch::Tensor> conv_bwd_pair(torch::Tensor dy, torch::Tensor w,
+                                         torch::Tensor x, int64_t R,
+                                         int64_t S, int64_t pad, int64_t H,
+                                         int64_t W, int64_t gkey);
 std::vector<torch::Tensor> head_xent_fwd(torch::Tensor h1, torch::Tensor w2,
                                          torch::Tensor b2,
                                          torch::Tensor labels,
@@ -239,6 +245,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "single-launch backward of the 2-layer dense head (M <= 32)");
     m.def("linear_bwd_pair", &linear_bwd_pair,
           "dense backward pair in one launch: (dx = dy.w, dw = dy^T.x)");
+    m.def("conv_bwd_pair_ok", &conv_bwd_pair_ok, py::arg("dy"), py::arg("w"),
+          py::arg("pad"), py::arg("H"), py::arg("W"),
+          "whether conv_bwd_pair runs the single paired launch");
+    m.def("conv_bwd_pair", &conv_bwd_pair, py::arg("dy"), py::arg("w"),
+          py::arg("x"), py::arg("R"), py::arg("S"), py::arg("pad"),
+          py::arg("H"), py::arg("W"), py::arg("gkey") = 0,
+          "conv dgrad + wgrad in one launch: (dx, dw)");
     m.def("head_xent_fwd", &head_xent_fwd,
           "classifier tail forward: (logits, probs, loss), M<=64 H<=128 C<=16");
     m.def("head_xent_bwd", &head_xent_bwd,

@@ -24,6 +24,14 @@
 //   conv_dgrad_kernel/_glds_       dgrad, K reordered to (r,s,ko) for
 //                                  contiguous dy gathers
 //   conv_wgrad_kernel/_glds_       wgrad, pixel-major tiles, split-K slabs
+//   conv_dgrad_glds_body / conv_wgrad_glds_k32_body
+//                                  the glds dgrad / k32 wgrad tiles as
+//                                  __device__ bodies over an LDS base and
+//                                  virtual block coordinates
+//   conv_bwd_pair_kernel           dgrad + wgrad of one small conv in ONE
+//                                  launch, role by block index, one LDS
+//                                  buffer sized to the larger role
+//                                  (conv_bwd_pair)
 //   conv_wgrad_small_kernel        Kout<=64 & RSC<=16 first-layer wgrad:
 //                                  waves split over pixels, LDS reduce
 //   sum_slabs_f32_kernel           lane-parallel split-K slab reduction
@@ -1191,15 +1199,21 @@ conv_dgrad_kernel(const unsigned short* __restrict__ dy,
 // ---- glds-pipelined dgrad (same 2-buffer DMA structure as fwd; B tile is
 // k-major so its staging is also lane-linear). Requires stride==1 paths NOT
 // needed: S1 handled in the source-address computation. ----
+// The tile body is a __device__ template over an LDS base pointer and
+// VIRTUAL block coordinates (bx, by, bz) / M-tile extent gx, so the
+// stand-alone kernel below and conv_bwd_pair_kernel run the same code
+// (as gemm_tile_body serves gemm_kernel). gx feeds xcd_remap: it is the
+// dgrad role's own M-tile count, not the launching grid's.
 template <int BM, int BN, int WM, int WN, int FM, int FN, bool S1>
-__global__ void __launch_bounds__(TPB)
-conv_dgrad_glds_kernel(const unsigned short* __restrict__ dy,
-                       const unsigned short* __restrict__ w,
-                       unsigned short* __restrict__ dx,
-                       float* __restrict__ dx32,
-                       const unsigned short* __restrict__ zbuf, ConvShape s,
-                       int k_chunks) {
-    __shared__ unsigned short smem[3 * (BM + BN) * 32];
+__device__ __forceinline__ void
+conv_dgrad_glds_body(unsigned short* smem, const int bx, const int by,
+                     const int bz, const int gx,
+                     const unsigned short* __restrict__ dy,
+                     const unsigned short* __restrict__ w,
+                     unsigned short* __restrict__ dx,
+                     float* __restrict__ dx32,
+                     const unsigned short* __restrict__ zbuf,
+                     const ConvShape& s, const int k_chunks) {
     auto As = [&](int buf) -> unsigned short (*)[32] {
         return reinterpret_cast<unsigned short(*)[32]>(smem + buf * (BM + BN) * 32);
     };
@@ -1211,8 +1225,8 @@ conv_dgrad_glds_kernel(const unsigned short* __restrict__ dy,
     const int tid = threadIdx.x;
     const int wave = tid >> 6;
     const int lane = tid & 63;
-    const int m0 = xcd_remap(blockIdx.x, gridDim.x) * BM;
-    const int n0 = blockIdx.y * BN;
+    const int m0 = xcd_remap(bx, gx) * BM;
+    const int n0 = by * BN;
     const int M = s.N * s.H * s.W;
     const int KK = s.Kout * s.R * s.S;
 
@@ -1280,7 +1294,7 @@ conv_dgrad_glds_kernel(const unsigned short* __restrict__ dy,
 
     const int ksteps = (KK + 31) / 32;
     const int kc_len = (ksteps + k_chunks - 1) / k_chunks;
-    const int kbeg = blockIdx.z * kc_len * 32;
+    const int kbeg = bz * kc_len * 32;
     const int kend = min(kbeg + kc_len * 32, KK);
     // 3-buffer counted-vmcnt pipeline (see conv_fwd_glds_kernel)
     stage(0, kbeg);
@@ -1336,6 +1350,20 @@ conv_dgrad_glds_kernel(const unsigned short* __restrict__ dy,
                     dx[(int64_t)row * s.C + col] = f2bf(acc[i][j][r]);
             }
     }
+}
+
+template <int BM, int BN, int WM, int WN, int FM, int FN, bool S1>
+__global__ void __launch_bounds__(TPB)
+conv_dgrad_glds_kernel(const unsigned short* __restrict__ dy,
+                       const unsigned short* __restrict__ w,
+                       unsigned short* __restrict__ dx,
+                       float* __restrict__ dx32,
+                       const unsigned short* __restrict__ zbuf, ConvShape s,
+                       int k_chunks) {
+    __shared__ unsigned short smem[3 * (BM + BN) * 32];
+    conv_dgrad_glds_body<BM, BN, WM, WN, FM, FN, S1>(
+        smem, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, dy, w, dx, dx32,
+        zbuf, s, k_chunks);
 }
 
 // f32 accumulator -> bf16 (no bias/relu): split-K epilogue for dgrad.
@@ -1665,16 +1693,19 @@ conv_wgrad_glds_kernel(const unsigned short* __restrict__ dy,
 // per barrier, no ko waste, half the barriers per pixel. Pipeline and
 // gather structure mirror conv_wgrad_glds_kernel (3-buffer counted
 // vmcnt(3): three 16-B glds per thread per stage). ----
+// Body over an LDS base pointer and virtual block coordinates, shared by the
+// stand-alone kernel and conv_bwd_pair_kernel (see conv_dgrad_glds_body).
 template <int BN, int WM, int WN, int FM, int FN, int BKP = 64>
-__global__ void __launch_bounds__(TPB)
-conv_wgrad_glds_k32_kernel(const unsigned short* __restrict__ dy,
-                           const unsigned short* __restrict__ x,
-                           float* __restrict__ dw,
-                           const unsigned short* __restrict__ zbuf,
-                           ConvShape s, int k_chunks) {
+__device__ __forceinline__ void
+conv_wgrad_glds_k32_body(unsigned short* smem, const int bx, const int by,
+                         const int bz,
+                         const unsigned short* __restrict__ dy,
+                         const unsigned short* __restrict__ x,
+                         float* __restrict__ dw,
+                         const unsigned short* __restrict__ zbuf,
+                         const ConvShape& s, const int k_chunks) {
     // BKP = pixels per K-step (64 or 128; 128 halves the barrier count
-    // again at 3 LDS buffers x 24 KB)
-    __shared__ unsigned short smem[3 * (32 + BN) * BKP];
+    // again at 3 LDS buffers x 24 KB); smem holds 3 * (32 + BN) * BKP
     auto Dys = [&](int buf) -> unsigned short (*)[32] {
         return reinterpret_cast<unsigned short(*)[32]>(
             smem + buf * (32 + BN) * BKP);
@@ -1686,13 +1717,13 @@ conv_wgrad_glds_k32_kernel(const unsigned short* __restrict__ dy,
     const int tid = threadIdx.x;
     const int wave = tid >> 6;
     const int lane = tid & 63;
-    const int m0 = blockIdx.x * 32;   // over Kout
-    const int n0 = blockIdx.y * BN;   // over RSC
+    const int m0 = bx * 32;   // over Kout
+    const int n0 = by * BN;   // over RSC
     const int M = s.Kout;
     const int NN = s.R * s.S * s.C;
     const int KK = s.N * s.OH * s.OW;
     const int chunk = (KK + k_chunks - 1) / k_chunks;
-    const int kbeg = blockIdx.z * chunk;
+    const int kbeg = bz * chunk;
     const int kend = min(kbeg + chunk, KK);
 
     auto stage = [&](int buf, int k0) {
@@ -1804,6 +1835,54 @@ conv_wgrad_glds_k32_kernel(const unsigned short* __restrict__ dy,
                 else
                     dw[(int64_t)ko * NN + col] = acc[i][j][r];
             }
+    }
+}
+
+template <int BN, int WM, int WN, int FM, int FN, int BKP = 64>
+__global__ void __launch_bounds__(TPB)
+conv_wgrad_glds_k32_kernel(const unsigned short* __restrict__ dy,
+                           const unsigned short* __restrict__ x,
+                           float* __restrict__ dw,
+                           const unsigned short* __restrict__ zbuf,
+                           ConvShape s, int k_chunks) {
+    __shared__ unsigned short smem[3 * (32 + BN) * BKP];
+    conv_wgrad_glds_k32_body<BN, WM, WN, FM, FN, BKP>(
+        smem, blockIdx.x, blockIdx.y, blockIdx.z, dy, x, dw, zbuf, s,
+        k_chunks);
+}
+
+// ---- dgrad + wgrad of ONE conv in one launch (small layers only: the host
+// pairs when both roles' blocks together fit one per CU, so the union's
+// LDS/register footprint cannot cost occupancy). Both depend only on dy and
+// not on each other; run as two launches the second waits behind the first
+// while each leaves most of the chip idle. A linear block index picks the
+// role: [0, n_dgrad) run the stride-1 glds dgrad tile (single k-chunk), the
+// rest the k32 wgrad tile with (y, z) decoded from the remainder. ONE raw
+// LDS buffer sized to the larger role (wgrad: 72 KB; dgrad uses 24 KB of
+// it) — two static arrays would sum. The tile bodies are the stand-alone
+// kernels' own, so every output bit and every atomic is the same. ----
+__global__ void __launch_bounds__(TPB)
+conv_bwd_pair_kernel(const unsigned short* __restrict__ dy,
+                     const unsigned short* __restrict__ w,
+                     const unsigned short* __restrict__ x,
+                     unsigned short* __restrict__ dx, float* __restrict__ dw,
+                     const unsigned short* __restrict__ zbuf, ConvShape s,
+                     int n_dgrad, int dgrad_gx, int wgrad_gy, int wgrad_kc) {
+    constexpr int LDS_DGRAD = 3 * (64 + 64) * 32;
+    constexpr int LDS_WGRAD = 3 * (32 + 64) * 128;
+    __shared__ unsigned short smem[LDS_WGRAD > LDS_DGRAD ? LDS_WGRAD
+                                                         : LDS_DGRAD];
+    const int bid = blockIdx.x;
+    if (bid < n_dgrad) {
+        const int by = bid / dgrad_gx;
+        conv_dgrad_glds_body<64, 64, 2, 2, 2, 2, true>(
+            smem, bid - by * dgrad_gx, by, 0, dgrad_gx, dy, w, dx, nullptr,
+            zbuf, s, 1);
+    } else {
+        const int r = bid - n_dgrad;
+        const int bz = r / wgrad_gy;
+        conv_wgrad_glds_k32_body<64, 2, 2, 1, 2, 128>(
+            smem, 0, r - bz * wgrad_gy, bz, dy, x, dw, zbuf, s, wgrad_kc);
     }
 }
 
@@ -4421,6 +4500,39 @@ conv2d_relu_pool_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,
     return {p, idx, (int64_t)s.OH, (int64_t)s.OW};
 }
 
+// conv2d_dgrad's dispatch predicates. They live here and nowhere else:
+// conv2d_dgrad launches what they say and conv_bwd_pair's envelope asks the
+// same functions, so the two cannot drift apart. `s` is the conv's own
+// shape (H/W input extent, OH/OW = dy extent).
+static bool dgrad_takes_tile3(const ConvShape& s) {
+    const char* t3env_d = getenv("HEFL_TILE3");
+    const int t3mode_d = t3env_d ? t3env_d[0] - '0' : 1;
+    if (!(t3mode_d != 0 && s.R == 3 && s.S == 3 && s.stride == 1 &&
+          s.pad <= 1 && s.Kout % 32 == 0 && s.C > 16 &&
+          (t3mode_d == 2 || s.C <= 32)))
+        return false;
+    const int BN3 = s.C <= 32 ? 32 : 64;
+    const int kt = ceildiv(s.C, BN3);
+    const int64_t min_tiles = t3mode_d == 2 ? 1 : 256;
+    const int64_t t16 = (int64_t)s.N * ceildiv(s.H, 16) * ceildiv(s.W, 16)
+                        * kt;
+    return s.H >= 12 && t16 >= min_tiles;
+}
+
+static bool dgrad_glds_ok(const ConvShape& s) {
+    return s.C >= 16 && s.C % 8 == 0 && s.Kout % 8 == 0;
+}
+
+static int dgrad_glds_chunks(const ConvShape& s) {
+    const int M = s.N * s.H * s.W;
+    const int tiles = ceildiv(M, 64) * ceildiv(s.C, 64);
+    const int ksteps = ceildiv(s.Kout * s.R * s.S, 32);
+    int k_chunks = 1;
+    if (tiles < 256 && ksteps >= 16)
+        k_chunks = std::max(1, std::min(ksteps / 4, 512 / tiles));
+    return k_chunks;
+}
+
 torch::Tensor conv2d_dgrad(torch::Tensor dy, torch::Tensor w, int64_t stride,
                            int64_t H, int64_t W, int64_t pad) {
     CHECK_GPU(dy);
@@ -4439,10 +4551,7 @@ torch::Tensor conv2d_dgrad(torch::Tensor dy, torch::Tensor w, int64_t stride,
     // dgrad as a direct tiled conv of dy with the 180-rotated transposed
     // weights: dx = conv3x3(dy, wT, pad' = 2 - pad). Same winner shape
     // class as forward (output channels <= 32 -> the BN=32 16x16 tile).
-    const char* t3env_d = getenv("HEFL_TILE3");
-    const int t3mode_d = t3env_d ? t3env_d[0] - '0' : 1;
-    if (t3mode_d != 0 && s.R == 3 && s.S == 3 && stride == 1 && pad <= 1 &&
-        s.Kout % 32 == 0 && C > 16 && (t3mode_d == 2 || C <= 32)) {
+    if (dgrad_takes_tile3(s)) {
         ConvShape s3;
         s3.N = N; s3.H = s.OH; s3.W = s.OW; s3.C = s.Kout;
         s3.Kout = C; s3.R = 3; s3.S = 3; s3.stride = 1; s3.pad = 2 - (int)pad;
@@ -4450,10 +4559,7 @@ torch::Tensor conv2d_dgrad(torch::Tensor dy, torch::Tensor w, int64_t stride,
         fill_magic(s3);
         const int BN3 = C <= 32 ? 32 : 64;
         const int kt = ceildiv(C, BN3);
-        const int64_t min_tiles = t3mode_d == 2 ? 1 : 256;
-        const int64_t t16 = (int64_t)N * ceildiv(s3.OH, 16)
-                            * ceildiv(s3.OW, 16) * kt;
-        if (s3.OH >= 12 && t16 >= min_tiles) {
+        {
             auto wT = torch::empty({C, 3, 3, s.Kout}, w.options());
             const int64_t tot = (int64_t)C * 9 * s.Kout;
             hipLaunchKernelGGL(rot180_transpose_w_kernel,
@@ -4479,16 +4585,11 @@ torch::Tensor conv2d_dgrad(torch::Tensor dy, torch::Tensor w, int64_t stride,
     // config #2 (38.45 vs 38.44 rounds/s) — the BN=64 tile wastes 3/4 of
     // its columns, which cancels the 16-B-vector advantage over the
     // generic gather at this width. Kept for the uniform path.
-    if (C >= 16 && C % 8 == 0 && s.Kout % 8 == 0) {
+    if (dgrad_glds_ok(s)) {
         static torch::Tensor zbuf;
         if (!zbuf.defined() || zbuf.device() != dy.device())
             zbuf = torch::zeros({8}, dy.options());
-        const int KKd = s.Kout * s.R * s.S;
-        int tiles = ceildiv(M, 64) * ceildiv(C, 64);
-        int ksteps = ceildiv(KKd, 32);
-        int k_chunks = 1;
-        if (tiles < 256 && ksteps >= 16)
-            k_chunks = std::max(1, std::min(ksteps / 4, 512 / tiles));
+        const int k_chunks = dgrad_glds_chunks(s);
         dim3 grid(ceildiv(M, 64), ceildiv(C, 64), k_chunks);
         torch::Tensor dx32;
         float* dx32p = nullptr;
@@ -4545,6 +4646,32 @@ torch::Tensor conv2d_dgrad(torch::Tensor dy, torch::Tensor w, int64_t stride,
     return dx;
 }
 
+// conv2d_wgrad's k32 dispatch predicates, shared with conv_bwd_pair's
+// envelope (same single-source rule as the dgrad predicates above).
+static bool wgrad_takes_k32(const ConvShape& s) {
+    const int NN = s.R * s.S * s.C;
+    return NN > 16 && s.C % 8 == 0 && s.Kout % 8 == 0 && s.Kout <= 32;
+}
+
+// 128-pixel K-steps measured +3-5% over 64 after the staging fix (the first
+// +15% probe was staging only half the Xs tile — a timing-only A/B hides
+// correctness bugs); HEFL_K32B=0 for A/B
+static bool wgrad_k32_bkp128() {
+    static const bool bkp128 = [] {
+        const char* e = getenv("HEFL_K32B");
+        return !e || e[0] != '0';
+    }();
+    return bkp128;
+}
+
+static int wgrad_k32_chunks(const ConvShape& s) {
+    const int NN = s.R * s.S * s.C;
+    const int KK = s.N * s.OH * s.OW;
+    const int tiles32 = ceildiv(s.Kout, 32) * ceildiv(NN, 64);
+    return std::max(1, std::min(ceildiv(KK, 128),
+                                512 / std::max(tiles32, 1)));
+}
+
 torch::Tensor conv2d_wgrad(torch::Tensor dy, torch::Tensor x, int64_t stride,
                            int64_t R, int64_t S, int64_t pad,
                            int64_t gkey) {
@@ -4598,21 +4725,13 @@ torch::Tensor conv2d_wgrad(torch::Tensor dy, torch::Tensor x, int64_t stride,
                            dw.data_ptr<float>(), total, kc);
         return dw;
     }
-    if (glds_ok && s.Kout <= 32) {
+    if (wgrad_takes_k32(s)) {
         // 32-ko tile, 64-pixel K-step: no ko waste on 32-filter layers
         static torch::Tensor zbuf32;
         if (!zbuf32.defined() || zbuf32.device() != dy.device())
             zbuf32 = torch::zeros({8}, dy.options());
-        // 128-pixel K-steps measured +3-5% over 64 after the staging fix
-        // (the first +15% probe was staging only half the Xs tile — a
-        // timing-only A/B hides correctness bugs); HEFL_K32B=0 for A/B
-        static const bool bkp128 = [] {
-            const char* e = getenv("HEFL_K32B");
-            return !e || e[0] != '0';
-        }();
-        int tiles32 = ceildiv(s.Kout, 32) * ceildiv(NN, 64);
-        int kc = std::max(1, std::min(ceildiv(KK, 128),
-                                      512 / std::max(tiles32, 1)));
+        const bool bkp128 = wgrad_k32_bkp128();
+        const int kc = wgrad_k32_chunks(s);
         torch::Tensor dw32;
         bool pooled = false;
         if (kc > 1 && gkey)
@@ -4679,6 +4798,91 @@ torch::Tensor conv2d_wgrad(torch::Tensor dy, torch::Tensor x, int64_t stride,
                            dw.data_ptr<float>(), s, k_chunks);
     }
     return dw;
+}
+
+// Pairing envelope for conv_bwd_pair (testable from Python like
+// head_xent_ok): conv2d_dgrad would run the stride-1 glds tile unsplit,
+// conv2d_wgrad the 128-pixel k32 tile, and both roles' blocks together fit
+// one per CU — then the paired kernel's max-sized LDS/register footprint
+// cannot cost occupancy. Larger layers keep two launches.
+static bool conv_bwd_pair_plan(const ConvShape& s, int& n_dgrad, int& dgx,
+                               int& wgy, int& kc) {
+    if (s.stride != 1) return false;
+    if (dgrad_takes_tile3(s) || !dgrad_glds_ok(s) ||
+        dgrad_glds_chunks(s) != 1)
+        return false;
+    if (!wgrad_takes_k32(s) || !wgrad_k32_bkp128()) return false;
+    const int M = s.N * s.H * s.W;
+    dgx = ceildiv(M, 64);
+    n_dgrad = dgx * ceildiv(s.C, 64);
+    wgy = ceildiv(s.R * s.S * s.C, 64);
+    kc = wgrad_k32_chunks(s);
+    const int n_wgrad = ceildiv(s.Kout, 32) * wgy * kc;
+    const int cus = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+    return n_dgrad + n_wgrad <= cus;
+}
+
+static ConvShape conv_bwd_shape(const torch::Tensor& dy,
+                                const torch::Tensor& w, int64_t pad,
+                                int64_t H, int64_t W) {
+    ConvShape s;
+    s.N = (int)dy.size(0); s.H = (int)H; s.W = (int)W; s.C = (int)w.size(3);
+    s.Kout = (int)w.size(0); s.R = (int)w.size(1); s.S = (int)w.size(2);
+    s.stride = 1; s.pad = (int)pad;
+    s.OH = (int)dy.size(1); s.OW = (int)dy.size(2);
+    fill_magic(s);
+    return s;
+}
+
+bool conv_bwd_pair_ok(torch::Tensor dy, torch::Tensor w, int64_t pad,
+                      int64_t H, int64_t W) {
+    if (!dy.is_cuda()) return false;
+    int n_dgrad, dgx, wgy, kc;
+    return conv_bwd_pair_plan(conv_bwd_shape(dy, w, pad, H, W), n_dgrad, dgx,
+                              wgy, kc);
+}
+
+// dgrad + wgrad of one stride-1 conv: ONE conv_bwd_pair_kernel launch inside
+// the envelope above, conv2d_dgrad + conv2d_wgrad outside it. Same outputs
+// either way (the paired kernel runs the stand-alone kernels' tile bodies).
+std::vector<torch::Tensor> conv_bwd_pair(torch::Tensor dy, torch::Tensor w,
+                                         torch::Tensor x, int64_t R,
+                                         int64_t S, int64_t pad, int64_t H,
+                                         int64_t W, int64_t gkey) {
+    CHECK_GPU(dy);
+    TORCH_CHECK(dy.is_contiguous() && w.is_contiguous() && x.is_contiguous());
+    TORCH_CHECK(w.size(1) == R && w.size(2) == S && x.size(1) == H &&
+                x.size(2) == W && x.size(3) == w.size(3) &&
+                dy.size(3) == w.size(0) && x.size(0) == dy.size(0));
+    const ConvShape s = conv_bwd_shape(dy, w, pad, H, W);
+    int n_dgrad = 0, dgx = 0, wgy = 0, kc = 0;
+    if (!conv_bwd_pair_plan(s, n_dgrad, dgx, wgy, kc)) {
+        auto dx = conv2d_dgrad(dy, w, 1, H, W, pad);
+        auto dw = conv2d_wgrad(dy, x, 1, R, S, pad, gkey);
+        return {dx, dw};
+    }
+    auto stream = at::cuda::getCurrentCUDAStream();
+    static torch::Tensor zbuf;
+    if (!zbuf.defined() || zbuf.device() != dy.device())
+        zbuf = torch::zeros({8}, dy.options());
+    auto dx = torch::empty({(int64_t)s.N, H, W, (int64_t)s.C}, dy.options());
+    // dw allocation / grad_buf routing: conv2d_wgrad's k32 branch
+    torch::Tensor dw32;
+    bool pooled = false;
+    if (kc > 1 && gkey)
+        dw32 = grad_buf(gkey, {s.Kout, R, S, s.C}, x.options(), stream,
+                        pooled);
+    if (!pooled)
+        dw32 = kc > 1 ? torch::zeros({s.Kout, R, S, s.C},
+                                     x.options().dtype(torch::kFloat32))
+                      : torch::empty({s.Kout, R, S, s.C},
+                                     x.options().dtype(torch::kFloat32));
+    const int n_wgrad = ceildiv(s.Kout, 32) * wgy * kc;
+    hipLaunchKernelGGL(conv_bwd_pair_kernel, dim3(n_dgrad + n_wgrad),
+                       dim3(TPB), 0, stream, bf_ptr(dy), bf_ptr(w), bf_ptr(x),
+                       bf_ptr_mut(dx), dw32.data_ptr<float>(), bf_ptr(zbuf),
+                       s, n_dgrad, dgx, wgy, kc);
+    return {dx, dw32};
 }
 
 torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,

@@ -87,6 +87,11 @@ _LIN_PAIR = os.getenv("HEFL_LIN_PAIR", "1") != "0"
 # compares in the epilogue; the pre-pool activation is never written.
 # Bit-identical p / idx (tests/test_gpu_conv_pool_fused.py).
 _CONV_POOL = os.getenv("HEFL_CONV_POOL", "1") != "0"
+# Paired conv backward (default ON, HEFL_CONV_BWD_PAIR=0 restores the two
+# launches): dgrad and wgrad of a small conv in ONE launch, role by block
+# index, where both fit one block per CU (conv_bwd_pair_ok); same tile
+# bodies, same outputs (tests/test_gpu_conv_bwd_pair.py).
+_CONV_BWD_PAIR = os.getenv("HEFL_CONV_BWD_PAIR", "1") != "0"
 
 # Epoch-graph capture contract (fl/client.py sets this around warmup +
 # capture; HEFL_GRAPH_NO_ZERO=0 disables): while True, conv dw / bias db
@@ -259,7 +264,10 @@ class _ConvReluPoolFn(torch.autograd.Function):
     conv2d_fwd + maxpool2x2_fwd with identical results. Backward: ONE
     pool_relu_bias_bwd kernel produces the gated conv-activation gradient
     AND the bias gradient (replacing maxpool2x2_bwd + relu_bias_bwd, i.e.
-    two full passes over the activation-gradient tensor)."""
+    two full passes over the activation-gradient tensor); then dgrad and
+    wgrad, as ONE conv_bwd_pair launch where the layer is small enough for
+    both to fit one block per CU (conv_bwd_pair_ok; HEFL_CONV_BWD_PAIR=0 or
+    a larger layer: two launches, same outputs)."""
 
     @staticmethod
     def forward(ctx, x, w, b, pad: int):
@@ -291,12 +299,21 @@ class _ConvReluPoolFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, w, p, idx = ctx.saved_tensors
         ch, cw = ctx.conv_hw
+        Kout, R, S, C = w.shape
         bkey = ctx.bkey if GRAPH_NO_ZERO else 0
         dym, db = _C().pool_relu_bias_bwd(dy.contiguous(), idx, p, ch, cw,
                                           gkey=bkey)
         wg = ctx.wkey if (GRAPH_NO_ZERO and not ctx.cpad) else 0
         fork = (_BWD_FORK and ctx.needs_input_grad[0]
                 and torch.cuda.is_current_stream_capturing())
+        if (_CONV_BWD_PAIR and ctx.needs_input_grad[0] and not ctx.cpad
+                and not _BWD_FORK):
+            # one launch inside conv_bwd_pair_ok's envelope; outside it the
+            # wrapper runs conv2d_dgrad + conv2d_wgrad as below
+            dx, dw = _C().conv_bwd_pair(dym, w, x.contiguous(), R, S,
+                                        ctx.pad, x.shape[1], x.shape[2],
+                                        gkey=wg)
+            return dx, dw, db, None
         if fork:
             cur = torch.cuda.current_stream()
             side = _fork_side(dy.device)
@@ -331,6 +348,14 @@ def conv_relu_pool(x, w, b, pad: int = 0):
     if x.is_cuda:
         return _ConvReluPoolFn.apply(x, w, b, pad)
     return maxpool2x2(conv2d(x, w, b, 1, True, pad))
+
+
+def conv_bwd_pair_ok(dy, w, pad: int, H: int, W: int) -> bool:
+    """Whether conv_bwd_pair(dy, w, x[N,H,W,C], ...) runs its single paired
+    launch (cnn.hip conv_bwd_pair_plan): the stride-1 glds dgrad tile unsplit,
+    the k32 wgrad tile, and both roles' blocks together at most one per CU.
+    Outside it the same entry point runs conv2d_dgrad + conv2d_wgrad."""
+    return bool(dy.is_cuda and _C().conv_bwd_pair_ok(dy, w, pad, H, W))
 
 
 # ---------------------------------------------------------------------------
