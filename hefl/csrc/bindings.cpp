@@ -50,6 +50,20 @@ torch::Tensor galois_lift(torch::Tensor c, int64_t ginv, torch::Tensor qs,
 torch::Tensor galois_perm_add(torch::Tensor ct, torch::Tensor ks0,
                               torch::Tensor ks1, torch::Tensor perm,
                               torch::Tensor qs);
+std::vector<torch::Tensor> ks_inner_hoisted(torch::Tensor dig,
+                                            torch::Tensor keys,
+                                            torch::Tensor perm,
+                                            torch::Tensor qs,
+                                            torch::Tensor ratios);
+torch::Tensor galois_perm_add_many(torch::Tensor ct, torch::Tensor ks0,
+                                   torch::Tensor ks1, torch::Tensor perm,
+                                   torch::Tensor qs);
+std::vector<torch::Tensor> lt_inner(torch::Tensor dig, torch::Tensor keys,
+                                    torch::Tensor perm, torch::Tensor pt,
+                                    torch::Tensor qs, torch::Tensor ratios);
+torch::Tensor lt_finish(torch::Tensor ct, torch::Tensor ks0, torch::Tensor ks1,
+                        torch::Tensor pt, torch::Tensor perm, int64_t z0,
+                        torch::Tensor qs, torch::Tensor ratios);
 
 // fft.hip
 torch::Tensor fft_encode(torch::Tensor vals, torch::Tensor tw_enc,
@@ -190,6 +204,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "X -> X^g on key-switch digits [.., D, n], lifted to [.., D, Lp, n]");
     m.def("galois_perm_add", &galois_perm_add,
           "rotated ciphertext (c0[perm] + ks0, ks1) over [.., 2, L, n]");
+    m.def("ks_inner_hoisted", &ks_inner_hoisted,
+          "key-switch inner product of G Galois elements over one hoisted "
+          "digit tensor: (acc0, acc1) [G, R, Lp, n]");
+    m.def("galois_perm_add_many", &galois_perm_add_many,
+          "G rotated ciphertexts [G, R, 2, L, n] in one launch");
+    m.def("lt_inner", &lt_inner,
+          "diagonal-weighted hoisted inner product summed over G: "
+          "(acc0, acc1) [R, Lp, n]");
+    m.def("lt_finish", &lt_finish,
+          "linear transform: ks + sum_g pt_g * c0[perm_g], step-0 term of c1");
     m.def("fft_encode", &fft_encode,
           "CKKS special-FFT encode: f64 slots -> int64 coeffs");
     m.def("fft_decode", &fft_decode,

@@ -32,6 +32,10 @@
 //   galois_lift / galois_perm_add kernels    slot rotation: automorphism
 //                                            fused into the digit lift and
 //                                            into the final add
+//   ks_inner_hoisted / galois_perm_add_many  G rotations of one ciphertext
+//                                            from one digit decomposition
+//   lt_inner / lt_finish kernels             ct x plaintext-matrix: diagonals
+//                                            summed before a single mod-down
 //
 // Structure per row of length n (n = 2^6 .. 2^15):
 //  * stages whose butterfly span exceeds NBLK run in a strided global-memory
@@ -1013,6 +1017,261 @@ __global__ void galois_perm_add_kernel(const int64_t* __restrict__ ct,
     }
 }
 
+// ---------------------------------------------------------------------------
+// Hoisted rotations and the encrypted linear transform (rotate_many_data,
+// hefl/he/linear.py). The digit tensor dig [R, D, Lp, n] is the NTT of the
+// lifted digits of c1 with NO automorphism; sigma_g acts on it as the
+// NTT-domain permutation perm[g], so one decomposition serves every element.
+// Same gather form as above: V consecutive outputs per thread, 16-byte loads
+// of the contiguous operands and 16-byte stores at V = 2, gathered sources
+// read one by one with the index masked into [0, n).
+// ---------------------------------------------------------------------------
+
+// acc_c[g, r, i, k] = sum_d dig[r, d, i, perm[g, k]] * keys[g, d, c, i, k]
+// mod q_i for c in {0, 1}. keys is [G, D, 2, Lp, n], perm int32 [G, n];
+// acc0 / acc1 are [G, R, Lp, n]. One launch for all G elements.
+template <int V>
+__global__ void ks_inner_hoisted_kernel(const int64_t* __restrict__ dig,
+                                        const int64_t* __restrict__ keys,
+                                        const int32_t* __restrict__ perm,
+                                        int64_t* __restrict__ acc0,
+                                        int64_t* __restrict__ acc1,
+                                        int64_t total_vec, int64_t n, int D,
+                                        int Lp, int64_t R,
+                                        const int64_t* __restrict__ qs,
+                                        const int64_t* __restrict__ ratios) {
+    using Vec = I64Vec<V>;
+    const int64_t Lpn = (int64_t)Lp * n;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+         t < total_vec; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = t * V;              // index into acc's [G, R, Lp, n]
+        const int64_t k0 = o % n;
+        const int i = (int)((o / n) % Lp);
+        const int64_t gr = o / Lpn;
+        const int64_t row = gr % R;
+        const int64_t g = gr / R;
+        const uint64_t q = (uint64_t)qs[i];
+        const uint64_t r0 = (uint64_t)ratios[2 * i];
+        const uint64_t r1 = (uint64_t)ratios[2 * i + 1];
+        int64_t src[V];
+        uint64_t a0[V], a1[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            src[k] = (int64_t)perm[g * n + k0 + k] & (n - 1);
+            a0[k] = 0;
+            a1[k] = 0;
+        }
+        const int64_t* dig_row = dig + row * D * Lpn + (int64_t)i * n;
+        const int64_t* key_row = keys + g * D * 2 * Lpn + (int64_t)i * n + k0;
+        for (int d = 0; d < D; ++d) {
+            const Vec b0 = *reinterpret_cast<const Vec*>(
+                key_row + (int64_t)d * 2 * Lpn);
+            const Vec b1 = *reinterpret_cast<const Vec*>(
+                key_row + (int64_t)d * 2 * Lpn + Lpn);
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                const uint64_t x = (uint64_t)dig_row[(int64_t)d * Lpn + src[k]];
+                a0[k] = addmod_u64(a0[k], mulmod_barrett(x, (uint64_t)b0.v[k],
+                                                         q, r0, r1), q);
+                a1[k] = addmod_u64(a1[k], mulmod_barrett(x, (uint64_t)b1.v[k],
+                                                         q, r0, r1), q);
+            }
+        }
+        Vec y0, y1;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            y0.v[k] = (int64_t)a0[k];
+            y1.v[k] = (int64_t)a1[k];
+        }
+        *reinterpret_cast<Vec*>(acc0 + o) = y0;
+        *reinterpret_cast<Vec*>(acc1 + o) = y1;
+    }
+}
+
+// All G rotated ciphertexts assembled in one launch: ct is [R, 2, L, n],
+// ks0 / ks1 [G, R, L, n], perm int32 [G, n], out [G, R, 2, L, n]:
+//   out[g, r, 0, i, k] = ct[r, 0, i, perm[g, k]] + ks0[g, r, i, k]  mod q_i
+//   out[g, r, 1, i, k] = ks1[g, r, i, k]
+template <int V>
+__global__ void galois_perm_add_many_kernel(const int64_t* __restrict__ ct,
+                                            const int64_t* __restrict__ ks0,
+                                            const int64_t* __restrict__ ks1,
+                                            const int32_t* __restrict__ perm,
+                                            int64_t* __restrict__ out,
+                                            int64_t total_vec, int64_t n,
+                                            int L, int64_t R,
+                                            const int64_t* __restrict__ qs) {
+    using Vec = I64Vec<V>;
+    const int64_t Ln = (int64_t)L * n;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+         t < total_vec; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = t * V;              // index into ks0's [G, R, L, n]
+        const int64_t k0 = o % n;
+        const int l = (int)((o / n) % L);
+        const int64_t gr = o / Ln;
+        const int64_t row = gr % R;
+        const int64_t g = gr / R;
+        const uint64_t q = (uint64_t)qs[l];
+        const int64_t c0_row = row * 2 * Ln + (int64_t)l * n;
+        const int64_t out_row = gr * 2 * Ln + (int64_t)l * n;
+        const Vec a = *reinterpret_cast<const Vec*>(ks0 + o);
+        const Vec b = *reinterpret_cast<const Vec*>(ks1 + o);
+        Vec y;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int64_t src = (int64_t)perm[g * n + k0 + k] & (n - 1);
+            y.v[k] = (int64_t)addmod_u64((uint64_t)ct[c0_row + src],
+                                         (uint64_t)a.v[k], q);
+        }
+        *reinterpret_cast<Vec*>(out + out_row + k0) = y;
+        *reinterpret_cast<Vec*>(out + out_row + Ln + k0) = b;
+    }
+}
+
+// Linear-transform inner product, summed over the G keyed diagonals before
+// the single mod-down:
+//   acc_c[r, i, k] = sum_g pt[g, i, k] *
+//                    (sum_d dig[r, d, i, perm[g, k]] * keys[g, d, c, i, k])
+// mod q_i. The digit sum comes first, so each diagonal costs one multiply by
+// pt per component. pt is [G, Lp, n]; acc0 / acc1 are [R, Lp, n].
+template <int V>
+__global__ void lt_inner_kernel(const int64_t* __restrict__ dig,
+                                const int64_t* __restrict__ keys,
+                                const int32_t* __restrict__ perm,
+                                const int64_t* __restrict__ pt,
+                                int64_t* __restrict__ acc0,
+                                int64_t* __restrict__ acc1,
+                                int64_t total_vec, int64_t n, int D, int Lp,
+                                int G, const int64_t* __restrict__ qs,
+                                const int64_t* __restrict__ ratios) {
+    using Vec = I64Vec<V>;
+    const int64_t Lpn = (int64_t)Lp * n;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+         t < total_vec; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = t * V;              // index into acc's [R, Lp, n]
+        const int64_t k0 = o % n;
+        const int i = (int)((o / n) % Lp);
+        const int64_t row = o / Lpn;
+        const uint64_t q = (uint64_t)qs[i];
+        const uint64_t r0 = (uint64_t)ratios[2 * i];
+        const uint64_t r1 = (uint64_t)ratios[2 * i + 1];
+        const int64_t* dig_row = dig + row * D * Lpn + (int64_t)i * n;
+        uint64_t t0[V], t1[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            t0[k] = 0;
+            t1[k] = 0;
+        }
+        for (int g = 0; g < G; ++g) {
+            int64_t src[V];
+            uint64_t a0[V], a1[V];
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                src[k] = (int64_t)perm[(int64_t)g * n + k0 + k] & (n - 1);
+                a0[k] = 0;
+                a1[k] = 0;
+            }
+            const int64_t* key_row =
+                keys + (int64_t)g * D * 2 * Lpn + (int64_t)i * n + k0;
+            for (int d = 0; d < D; ++d) {
+                const Vec b0 = *reinterpret_cast<const Vec*>(
+                    key_row + (int64_t)d * 2 * Lpn);
+                const Vec b1 = *reinterpret_cast<const Vec*>(
+                    key_row + (int64_t)d * 2 * Lpn + Lpn);
+#pragma unroll
+                for (int k = 0; k < V; ++k) {
+                    const uint64_t x =
+                        (uint64_t)dig_row[(int64_t)d * Lpn + src[k]];
+                    a0[k] = addmod_u64(a0[k], mulmod_barrett(
+                        x, (uint64_t)b0.v[k], q, r0, r1), q);
+                    a1[k] = addmod_u64(a1[k], mulmod_barrett(
+                        x, (uint64_t)b1.v[k], q, r0, r1), q);
+                }
+            }
+            const Vec p = *reinterpret_cast<const Vec*>(
+                pt + (int64_t)g * Lpn + (int64_t)i * n + k0);
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                t0[k] = addmod_u64(t0[k], mulmod_barrett(
+                    a0[k], (uint64_t)p.v[k], q, r0, r1), q);
+                t1[k] = addmod_u64(t1[k], mulmod_barrett(
+                    a1[k], (uint64_t)p.v[k], q, r0, r1), q);
+            }
+        }
+        Vec y0, y1;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            y0.v[k] = (int64_t)t0[k];
+            y1.v[k] = (int64_t)t1[k];
+        }
+        *reinterpret_cast<Vec*>(acc0 + o) = y0;
+        *reinterpret_cast<Vec*>(acc1 + o) = y1;
+    }
+}
+
+// Linear-transform finish: the plaintext-weighted, permuted c0 terms of all
+// G diagonals (the step-0 one included) and the step-0 term of c1 added to
+// the mod-down outputs. ct is [R, 2, L, n] read in place, ks0 / ks1
+// [R, L, n], pt [G, L, n], perm int32 [G, n]; z0 is the index of the step-0
+// diagonal or -1:
+//   out[r, 0, i, k] = ks0[r, i, k] + sum_g pt[g, i, k] * ct[r, 0, i, perm[g, k]]
+//   out[r, 1, i, k] = ks1[r, i, k] + pt[z0, i, k] * ct[r, 1, i, k]
+template <int V>
+__global__ void lt_finish_kernel(const int64_t* __restrict__ ct,
+                                 const int64_t* __restrict__ ks0,
+                                 const int64_t* __restrict__ ks1,
+                                 const int64_t* __restrict__ pt,
+                                 const int32_t* __restrict__ perm,
+                                 int64_t* __restrict__ out,
+                                 int64_t total_vec, int64_t n, int L, int G,
+                                 int z0, const int64_t* __restrict__ qs,
+                                 const int64_t* __restrict__ ratios) {
+    using Vec = I64Vec<V>;
+    const int64_t Ln = (int64_t)L * n;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+         t < total_vec; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = t * V;              // index into ks0's [R, L, n]
+        const int64_t k0 = o % n;
+        const int l = (int)((o / n) % L);
+        const int64_t row = o / Ln;
+        const uint64_t q = (uint64_t)qs[l];
+        const uint64_t r0 = (uint64_t)ratios[2 * l];
+        const uint64_t r1 = (uint64_t)ratios[2 * l + 1];
+        const int64_t c0_row = row * 2 * Ln + (int64_t)l * n;
+        const Vec a = *reinterpret_cast<const Vec*>(ks0 + o);
+        const Vec b = *reinterpret_cast<const Vec*>(ks1 + o);
+        uint64_t y0[V], y1[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            y0[k] = (uint64_t)a.v[k];
+            y1[k] = (uint64_t)b.v[k];
+        }
+        for (int g = 0; g < G; ++g) {
+            const Vec p = *reinterpret_cast<const Vec*>(
+                pt + (int64_t)g * Ln + (int64_t)l * n + k0);
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                const int64_t src =
+                    (int64_t)perm[(int64_t)g * n + k0 + k] & (n - 1);
+                y0[k] = addmod_u64(y0[k], mulmod_barrett(
+                    (uint64_t)ct[c0_row + src], (uint64_t)p.v[k], q, r0, r1), q);
+                if (g == z0)
+                    y1[k] = addmod_u64(y1[k], mulmod_barrett(
+                        (uint64_t)ct[c0_row + Ln + k0 + k], (uint64_t)p.v[k],
+                        q, r0, r1), q);
+            }
+        }
+        Vec v0, v1;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            v0.v[k] = (int64_t)y0[k];
+            v1.v[k] = (int64_t)y1[k];
+        }
+        *reinterpret_cast<Vec*>(out + c0_row + k0) = v0;
+        *reinterpret_cast<Vec*>(out + c0_row + Ln + k0) = v1;
+    }
+}
+
 inline bool aligned16(const void* p) {
     return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
 }
@@ -1557,6 +1816,242 @@ torch::Tensor galois_perm_add(torch::Tensor ct, torch::Tensor ks0,
                            ks0.data_ptr<int64_t>(), ks1.data_ptr<int64_t>(),
                            perm.data_ptr<int32_t>(), out.data_ptr<int64_t>(),
                            tv, n, (int)L, qs.data_ptr<int64_t>());
+    }
+    return out;
+}
+
+namespace {
+
+// Shared argument checks of ks_inner_hoisted / lt_inner: dig [R, D, Lp, n],
+// keys [G, D, 2, Lp, n], perm int32 [G, n], prime tables of the Lp limbs.
+void check_hoisted_args(const torch::Tensor& dig, const torch::Tensor& keys,
+                        const torch::Tensor& perm, const torch::Tensor& qs,
+                        const torch::Tensor& ratios) {
+    CHECK_CUDA_OK(dig);
+    CHECK_CUDA_OK(keys);
+    CHECK_CUDA_OK(perm);
+    CHECK_CUDA_OK(qs);
+    CHECK_CUDA_OK(ratios);
+    TORCH_CHECK(dig.is_contiguous() && keys.is_contiguous() &&
+                perm.is_contiguous() && qs.is_contiguous() &&
+                ratios.is_contiguous(), "arguments must be contiguous");
+    TORCH_CHECK(dig.dtype() == torch::kInt64 && keys.dtype() == torch::kInt64 &&
+                qs.dtype() == torch::kInt64 && ratios.dtype() == torch::kInt64 &&
+                perm.dtype() == torch::kInt32,
+                "int64 tensors and an int32 perm expected");
+    TORCH_CHECK(dig.dim() == 4, "dig must be [R, D, Lp, n]");
+    const int64_t D = dig.size(1), Lp = dig.size(2), n = dig.size(3);
+    TORCH_CHECK(n >= 1 && (n & (n - 1)) == 0, "n must be a power of two");
+    TORCH_CHECK(D >= 1 && Lp >= 1 && dig.size(0) >= 1, "empty digit tensor");
+    TORCH_CHECK(keys.dim() == 5 && keys.size(0) >= 1 && keys.size(1) == D &&
+                keys.size(2) == 2 && keys.size(3) == Lp && keys.size(4) == n,
+                "keys must be [G, D, 2, Lp, n]");
+    TORCH_CHECK(perm.dim() == 2 && perm.size(0) == keys.size(0) &&
+                perm.size(1) == n, "perm must be int32 [G, n]");
+    TORCH_CHECK(qs.numel() == Lp && ratios.numel() == 2 * Lp,
+                "need prime / ratio tables of the Lp limbs");
+    TORCH_CHECK(keys.size(0) <= INT32_MAX / n, "too many Galois elements");
+}
+
+}  // namespace
+
+// dig [R, D, Lp, n] (hoisted NTT digits, no automorphism) x keys
+// [G, D, 2, Lp, n] under perm [G, n] -> (acc0, acc1) each [G, R, Lp, n].
+std::vector<torch::Tensor> ks_inner_hoisted(torch::Tensor dig,
+                                            torch::Tensor keys,
+                                            torch::Tensor perm,
+                                            torch::Tensor qs,
+                                            torch::Tensor ratios) {
+    check_hoisted_args(dig, keys, perm, qs, ratios);
+    const int64_t R = dig.size(0), D = dig.size(1), Lp = dig.size(2);
+    const int64_t n = dig.size(3), G = keys.size(0);
+    auto acc0 = torch::empty({G, R, Lp, n}, dig.options());
+    auto acc1 = torch::empty({G, R, Lp, n}, dig.options());
+    const int64_t total = acc0.numel();
+    auto stream = at::cuda::getCurrentCUDAStream();
+    // dig is only gathered (8-byte reads, any alignment)
+    const bool vec2 = n % 2 == 0 && aligned16(keys.data_ptr<int64_t>()) &&
+                      aligned16(acc0.data_ptr<int64_t>()) &&
+                      aligned16(acc1.data_ptr<int64_t>());
+    const int64_t tv = vec2 ? total / 2 : total;
+    int blocks = (int)std::min<int64_t>((tv + kThreads - 1) / kThreads, 4096);
+    if (vec2) {
+        hipLaunchKernelGGL(ks_inner_hoisted_kernel<2>, dim3(blocks),
+                           dim3(kThreads), 0, stream, dig.data_ptr<int64_t>(),
+                           keys.data_ptr<int64_t>(), perm.data_ptr<int32_t>(),
+                           acc0.data_ptr<int64_t>(), acc1.data_ptr<int64_t>(),
+                           tv, n, (int)D, (int)Lp, R, qs.data_ptr<int64_t>(),
+                           ratios.data_ptr<int64_t>());
+    } else {
+        hipLaunchKernelGGL(ks_inner_hoisted_kernel<1>, dim3(blocks),
+                           dim3(kThreads), 0, stream, dig.data_ptr<int64_t>(),
+                           keys.data_ptr<int64_t>(), perm.data_ptr<int32_t>(),
+                           acc0.data_ptr<int64_t>(), acc1.data_ptr<int64_t>(),
+                           tv, n, (int)D, (int)Lp, R, qs.data_ptr<int64_t>(),
+                           ratios.data_ptr<int64_t>());
+    }
+    return {acc0, acc1};
+}
+
+// ct [R, 2, L, n], ks0 / ks1 [G, R, L, n], perm int32 [G, n] -> the G
+// rotated ciphertexts [G, R, 2, L, n] = (c0[perm_g] + ks0_g, ks1_g).
+torch::Tensor galois_perm_add_many(torch::Tensor ct, torch::Tensor ks0,
+                                   torch::Tensor ks1, torch::Tensor perm,
+                                   torch::Tensor qs) {
+    CHECK_CUDA_OK(ct);
+    CHECK_CUDA_OK(ks0);
+    CHECK_CUDA_OK(ks1);
+    CHECK_CUDA_OK(perm);
+    CHECK_CUDA_OK(qs);
+    TORCH_CHECK(ct.is_contiguous() && ks0.is_contiguous() &&
+                ks1.is_contiguous() && perm.is_contiguous() &&
+                qs.is_contiguous(), "arguments must be contiguous");
+    TORCH_CHECK(ct.dtype() == torch::kInt64 && ks0.dtype() == torch::kInt64 &&
+                ks1.dtype() == torch::kInt64 && qs.dtype() == torch::kInt64 &&
+                perm.dtype() == torch::kInt32,
+                "int64 tensors and an int32 perm expected");
+    TORCH_CHECK(ct.dim() == 4 && ct.size(1) == 2, "ct must be [R, 2, L, n]");
+    const int64_t R = ct.size(0), L = ct.size(2), n = ct.size(3);
+    TORCH_CHECK(n >= 1 && (n & (n - 1)) == 0, "n must be a power of two");
+    TORCH_CHECK(R >= 1 && L >= 1 && qs.numel() >= L,
+                "limb count exceeds the prime table");
+    TORCH_CHECK(perm.dim() == 2 && perm.size(0) >= 1 && perm.size(1) == n,
+                "perm must be int32 [G, n]");
+    const int64_t G = perm.size(0);
+    TORCH_CHECK(G <= INT32_MAX / n, "too many Galois elements");
+    const std::vector<int64_t> ks_sizes = {G, R, L, n};
+    TORCH_CHECK(ks0.sizes().vec() == ks_sizes && ks1.sizes().vec() == ks_sizes,
+                "ks0 / ks1 must be [G, R, L, n]");
+    auto out = torch::empty({G, R, 2, L, n}, ct.options());
+    const int64_t total = ks0.numel();
+    auto stream = at::cuda::getCurrentCUDAStream();
+    const bool vec2 = n % 2 == 0 && aligned16(ks0.data_ptr<int64_t>()) &&
+                      aligned16(ks1.data_ptr<int64_t>()) &&
+                      aligned16(out.data_ptr<int64_t>());
+    const int64_t tv = vec2 ? total / 2 : total;
+    int blocks = (int)std::min<int64_t>((tv + kThreads - 1) / kThreads, 4096);
+    if (vec2) {
+        hipLaunchKernelGGL(galois_perm_add_many_kernel<2>, dim3(blocks),
+                           dim3(kThreads), 0, stream, ct.data_ptr<int64_t>(),
+                           ks0.data_ptr<int64_t>(), ks1.data_ptr<int64_t>(),
+                           perm.data_ptr<int32_t>(), out.data_ptr<int64_t>(),
+                           tv, n, (int)L, R, qs.data_ptr<int64_t>());
+    } else {
+        hipLaunchKernelGGL(galois_perm_add_many_kernel<1>, dim3(blocks),
+                           dim3(kThreads), 0, stream, ct.data_ptr<int64_t>(),
+                           ks0.data_ptr<int64_t>(), ks1.data_ptr<int64_t>(),
+                           perm.data_ptr<int32_t>(), out.data_ptr<int64_t>(),
+                           tv, n, (int)L, R, qs.data_ptr<int64_t>());
+    }
+    return out;
+}
+
+// ks_inner_hoisted weighted by the diagonals pt [G, Lp, n] and summed over
+// G: (acc0, acc1) each [R, Lp, n], ready for one mod-down.
+std::vector<torch::Tensor> lt_inner(torch::Tensor dig, torch::Tensor keys,
+                                    torch::Tensor perm, torch::Tensor pt,
+                                    torch::Tensor qs, torch::Tensor ratios) {
+    check_hoisted_args(dig, keys, perm, qs, ratios);
+    CHECK_CUDA_OK(pt);
+    TORCH_CHECK(pt.is_contiguous() && pt.dtype() == torch::kInt64,
+                "pt must be contiguous int64");
+    const int64_t R = dig.size(0), D = dig.size(1), Lp = dig.size(2);
+    const int64_t n = dig.size(3), G = keys.size(0);
+    TORCH_CHECK(pt.dim() == 3 && pt.size(0) == G && pt.size(1) == Lp &&
+                pt.size(2) == n, "pt must be [G, Lp, n]");
+    auto acc0 = torch::empty({R, Lp, n}, dig.options());
+    auto acc1 = torch::empty({R, Lp, n}, dig.options());
+    const int64_t total = acc0.numel();
+    auto stream = at::cuda::getCurrentCUDAStream();
+    const bool vec2 = n % 2 == 0 && aligned16(keys.data_ptr<int64_t>()) &&
+                      aligned16(pt.data_ptr<int64_t>()) &&
+                      aligned16(acc0.data_ptr<int64_t>()) &&
+                      aligned16(acc1.data_ptr<int64_t>());
+    const int64_t tv = vec2 ? total / 2 : total;
+    int blocks = (int)std::min<int64_t>((tv + kThreads - 1) / kThreads, 4096);
+    if (vec2) {
+        hipLaunchKernelGGL(lt_inner_kernel<2>, dim3(blocks), dim3(kThreads), 0,
+                           stream, dig.data_ptr<int64_t>(),
+                           keys.data_ptr<int64_t>(), perm.data_ptr<int32_t>(),
+                           pt.data_ptr<int64_t>(), acc0.data_ptr<int64_t>(),
+                           acc1.data_ptr<int64_t>(), tv, n, (int)D, (int)Lp,
+                           (int)G, qs.data_ptr<int64_t>(),
+                           ratios.data_ptr<int64_t>());
+    } else {
+        hipLaunchKernelGGL(lt_inner_kernel<1>, dim3(blocks), dim3(kThreads), 0,
+                           stream, dig.data_ptr<int64_t>(),
+                           keys.data_ptr<int64_t>(), perm.data_ptr<int32_t>(),
+                           pt.data_ptr<int64_t>(), acc0.data_ptr<int64_t>(),
+                           acc1.data_ptr<int64_t>(), tv, n, (int)D, (int)Lp,
+                           (int)G, qs.data_ptr<int64_t>(),
+                           ratios.data_ptr<int64_t>());
+    }
+    return {acc0, acc1};
+}
+
+// ct [R, 2, L, n], ks0 / ks1 [R, L, n] (the mod-down of lt_inner's sums),
+// pt [G, L, n], perm int32 [G, n], z0 = index of the step-0 diagonal or -1
+// -> transformed ciphertext [R, 2, L, n].
+torch::Tensor lt_finish(torch::Tensor ct, torch::Tensor ks0, torch::Tensor ks1,
+                        torch::Tensor pt, torch::Tensor perm, int64_t z0,
+                        torch::Tensor qs, torch::Tensor ratios) {
+    CHECK_CUDA_OK(ct);
+    CHECK_CUDA_OK(ks0);
+    CHECK_CUDA_OK(ks1);
+    CHECK_CUDA_OK(pt);
+    CHECK_CUDA_OK(perm);
+    CHECK_CUDA_OK(qs);
+    CHECK_CUDA_OK(ratios);
+    TORCH_CHECK(ct.is_contiguous() && ks0.is_contiguous() &&
+                ks1.is_contiguous() && pt.is_contiguous() &&
+                perm.is_contiguous() && qs.is_contiguous() &&
+                ratios.is_contiguous(), "arguments must be contiguous");
+    TORCH_CHECK(ct.dtype() == torch::kInt64 && ks0.dtype() == torch::kInt64 &&
+                ks1.dtype() == torch::kInt64 && pt.dtype() == torch::kInt64 &&
+                qs.dtype() == torch::kInt64 && ratios.dtype() == torch::kInt64 &&
+                perm.dtype() == torch::kInt32,
+                "int64 tensors and an int32 perm expected");
+    TORCH_CHECK(ct.dim() == 4 && ct.size(1) == 2, "ct must be [R, 2, L, n]");
+    const int64_t R = ct.size(0), L = ct.size(2), n = ct.size(3);
+    TORCH_CHECK(n >= 1 && (n & (n - 1)) == 0, "n must be a power of two");
+    TORCH_CHECK(R >= 1 && L >= 1 && qs.numel() >= L &&
+                ratios.numel() >= 2 * L, "limb count exceeds the prime table");
+    const std::vector<int64_t> ks_sizes = {R, L, n};
+    TORCH_CHECK(ks0.sizes().vec() == ks_sizes && ks1.sizes().vec() == ks_sizes,
+                "ks0 / ks1 must be [R, L, n]");
+    TORCH_CHECK(pt.dim() == 3 && pt.size(0) >= 1 && pt.size(1) == L &&
+                pt.size(2) == n, "pt must be [G, L, n]");
+    const int64_t G = pt.size(0);
+    TORCH_CHECK(G <= INT32_MAX / n, "too many diagonals");
+    TORCH_CHECK(perm.dim() == 2 && perm.size(0) == G && perm.size(1) == n,
+                "perm must be int32 [G, n]");
+    TORCH_CHECK(z0 >= -1 && z0 < G, "z0 must index a diagonal or be -1");
+    auto out = torch::empty_like(ct);
+    const int64_t total = ks0.numel();
+    auto stream = at::cuda::getCurrentCUDAStream();
+    // ct is read one coefficient at a time (c0 gathered, c1 in place)
+    const bool vec2 = n % 2 == 0 && aligned16(ks0.data_ptr<int64_t>()) &&
+                      aligned16(ks1.data_ptr<int64_t>()) &&
+                      aligned16(pt.data_ptr<int64_t>()) &&
+                      aligned16(out.data_ptr<int64_t>());
+    const int64_t tv = vec2 ? total / 2 : total;
+    int blocks = (int)std::min<int64_t>((tv + kThreads - 1) / kThreads, 4096);
+    if (vec2) {
+        hipLaunchKernelGGL(lt_finish_kernel<2>, dim3(blocks), dim3(kThreads),
+                           0, stream, ct.data_ptr<int64_t>(),
+                           ks0.data_ptr<int64_t>(), ks1.data_ptr<int64_t>(),
+                           pt.data_ptr<int64_t>(), perm.data_ptr<int32_t>(),
+                           out.data_ptr<int64_t>(), tv, n, (int)L, (int)G,
+                           (int)z0, qs.data_ptr<int64_t>(),
+                           ratios.data_ptr<int64_t>());
+    } else {
+        hipLaunchKernelGGL(lt_finish_kernel<1>, dim3(blocks), dim3(kThreads),
+                           0, stream, ct.data_ptr<int64_t>(),
+                           ks0.data_ptr<int64_t>(), ks1.data_ptr<int64_t>(),
+                           pt.data_ptr<int64_t>(), perm.data_ptr<int32_t>(),
+                           out.data_ptr<int64_t>(), tv, n, (int)L, (int)G,
+                           (int)z0, qs.data_ptr<int64_t>(),
+                           ratios.data_ptr<int64_t>());
     }
     return out;
 }

@@ -267,6 +267,35 @@ class GpuBackend:
         return self._C.galois_perm_add(ct.contiguous(), ks0.contiguous(),
                                        ks1.contiguous(), perm, self.qs)
 
+    # ----- hoisted rotations + linear transform (rotate_many, linear.py) -----
+    def ks_inner_hoisted(self, dig: torch.Tensor, keys: torch.Tensor,
+                         perm: torch.Tensor, tb: "LevelTables"):
+        """dig [R, l, l+1, n] (no automorphism) x keys [G, l, 2, l+1, n]
+        under the NTT-domain permutations perm [G, n] -> (acc0, acc1), each
+        [G, R, l+1, n]. One launch for all G elements."""
+        return self._C.ks_inner_hoisted(dig, keys, perm, tb.qs, tb.ratio_words)
+
+    def galois_perm_add_many(self, ct: torch.Tensor, ks0: torch.Tensor,
+                             ks1: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
+        """ct [R, 2, l, n], ks0 / ks1 [G, R, l, n], perm [G, n] -> the G
+        rotated ciphertexts [G, R, 2, l, n]. One launch."""
+        return self._C.galois_perm_add_many(ct.contiguous(), ks0.contiguous(),
+                                            ks1.contiguous(), perm, self.qs)
+
+    def lt_inner(self, dig: torch.Tensor, keys: torch.Tensor,
+                 perm: torch.Tensor, pt: torch.Tensor, tb: "LevelTables"):
+        """ks_inner_hoisted weighted by the diagonals pt [G, l+1, n] and
+        summed over G -> (acc0, acc1), each [R, l+1, n]. One launch."""
+        return self._C.lt_inner(dig, keys, perm, pt, tb.qs, tb.ratio_words)
+
+    def lt_finish(self, ct: torch.Tensor, ks0: torch.Tensor, ks1: torch.Tensor,
+                  pt: torch.Tensor, perm: torch.Tensor, z0: int) -> torch.Tensor:
+        """(ks0 + sum_g pt_g * c0[perm_g], ks1 + pt_z0 * c1) as [R, 2, l, n];
+        pt [G, l, n], z0 the step-0 diagonal's index or -1. One launch."""
+        return self._C.lt_finish(ct.contiguous(), ks0.contiguous(),
+                                 ks1.contiguous(), pt, perm, int(z0), self.qs,
+                                 self.ratio_words)
+
 
 @dataclass
 class LevelTables:
@@ -1149,7 +1178,7 @@ class CKKSContext:
             raise ValueError(
                 f"switching key must be [{self.L}, 2, {self.L + 1}, {self.n}], "
                 f"got {tuple(key.shape)}")
-        n, P = self.n, self.special
+        n = self.n
         gt = None if g is None else self._galois_tables(g)
         idx = list(range(l)) + [self.L]
         if self.device.type == "cuda":
@@ -1168,14 +1197,7 @@ class CKKSContext:
             be.ntt_level_(dig, tb)                     # [..., l, l+1, n]
             acc0, acc1 = be._C.ks_inner(dig, kl, tb.qs, tb.ratio_words,
                                         l, l + 1, n)
-            outs = []
-            for acc in (acc0, acc1):
-                cl = be.ntt(acc[..., l, :], self.L, inverse=True)
-                r_ntt = be.ntt_all(be.bcast_center_mod(cl, P, l))
-                diff = be.modsub_limbs(acc, r_ntt, l)
-                outs.append(be._C.modmul_scalar_limbs(
-                    diff, tb.pinv, tb.pinv_shoup, be.qs, l, n))
-            return outs[0], outs[1]
+            return self._moddown_level(acc0, acc1, l)
         lead = x.shape[:-2]
         acc0 = torch.zeros(lead + (l + 1, n), dtype=torch.int64, device=x.device)
         acc1 = torch.zeros_like(acc0)
@@ -1193,7 +1215,25 @@ class CKKSContext:
                 acc1[..., j, :] = torch.remainder(
                     acc1[..., j, :] + self.backend.modmul(
                         dig, key[d, 1, i].expand_as(dig).contiguous(), i), q)
-        # mod-down by P, as in _keyswitch: P sits at position l here
+        return self._moddown_level(acc0, acc1, l)
+
+    def _moddown_level(self, acc0: torch.Tensor, acc1: torch.Tensor, l: int):
+        """Mod-down by P of the key-switch accumulators [..., l+1, n] over
+        the limbs {q_0..q_{l-1}, P} (P at position l) -> (ks0, ks1), each
+        [..., l, n]. Any leading shape: a batch of Galois elements goes
+        through in the same launches as one."""
+        n, P = self.n, self.special
+        if self.device.type == "cuda":
+            be = self.backend
+            tb = be.level_tables(l)
+            outs = []
+            for acc in (acc0, acc1):
+                cl = be.ntt(acc[..., l, :], self.L, inverse=True)
+                r_ntt = be.ntt_all(be.bcast_center_mod(cl, P, l))
+                diff = be.modsub_limbs(acc, r_ntt, l)
+                outs.append(be._C.modmul_scalar_limbs(
+                    diff, tb.pinv, tb.pinv_shoup, be.qs, l, n))
+            return outs[0], outs[1]
         P_half = P // 2
         outs = []
         for acc in (acc0, acc1):
@@ -1314,6 +1354,177 @@ class CKKSContext:
     def sum_slots_tensor(self, ct: CtxtTensor, gk, width: int) -> CtxtTensor:
         return CtxtTensor(self.sum_slots_data(ct.data, gk, width), ct.scale,
                           ct.count)
+
+    # ----- hoisted multi-step rotations -----
+    # Everything of a rotation's key-switch up to and including the digit
+    # NTTs is independent of the Galois element when the automorphism is
+    # applied AFTER the lift: on the NTT-form digits sigma_g is the
+    # permutation perm_g. One decomposition D of c1 then serves every step,
+    #   acc_g[c, i, k] = sum_d D[d, i, perm_g[k]] * key_g[d, c, i, k]  mod q_i,
+    # and the mod-down runs once over the whole [G, R] batch. The permuted
+    # digit is the transform of the SIGNED sigma_g of the lifted digit (-v at
+    # a wrapped coefficient) where rotate_data lifts q_d - v: the two differ
+    # by q_d there, both are congruent to sigma_g(c) mod q_d with |digit| <
+    # q_d, so the result is a valid rotation under the same noise bound but
+    # not bit-identical to rotate_data's.
+    @staticmethod
+    def _dot_mod(a: torch.Tensor, b: torch.Tensor, q: int, dim: int) -> torch.Tensor:
+        """Exact sum over `dim` of a * b mod q (broadcasting, python ints):
+        the CPU oracle's inner product."""
+        r = (a.cpu().numpy().astype(object)
+             * b.cpu().numpy().astype(object)).sum(axis=dim) % q
+        return torch.from_numpy(r.astype(np.int64))
+
+    def _hoist_digits(self, c1: torch.Tensor, l: int) -> torch.Tensor:
+        """NTT-form key-switch digits of c1 [..., l, n] with no automorphism:
+        D[.., d, j, :] = NTT(c_d mod q_j) over the limbs {q_0..q_{l-1}, P},
+        c_d = INTT(c1[.., d, :]) in [0, q_d). Returns [..., l, l+1, n]."""
+        if c1.shape[-2] != l or not 1 <= l <= self.L:
+            raise ValueError(f"expected [.., {l}, n] with 1 <= l <= {self.L}, "
+                             f"got {tuple(c1.shape)}")
+        if self.device.type == "cuda":
+            be = self.backend
+            tb = be.level_tables(l)
+            c = be.ntt_all(c1, inverse=True)
+            dig = be._C.bcast_center_mod(c, 0, tb.qs, tb.ratio_words, l + 1)
+            return be.ntt_level_(dig, tb)
+        idx = list(range(l)) + [self.L]
+        dig = torch.empty(c1.shape[:-2] + (l, l + 1, self.n), dtype=torch.int64)
+        for d in range(l):
+            c = self.backend.ntt(c1[..., d, :], d, inverse=True)
+            for j, i in enumerate(idx):
+                dig[..., d, j, :] = self.backend.ntt(
+                    torch.remainder(c, self._q(i)), i)
+        return dig
+
+    def _galois_stack(self, elements: Sequence[int], gk, l: int):
+        """(keys [G, l, 2, l+1, n], perm32 [G, n], perm [G, n]) of the given
+        Galois elements at level l, stacked once per (elements, level) and
+        cached the way _key_at_level caches: the entry holds the key tensors
+        it was built from and is rebuilt when any of them is another object."""
+        elements = tuple(int(g) for g in elements)
+        src = tuple(gk[g] for g in elements)
+        cache = self.__dict__.setdefault("_galois_stack_cache", {})
+        hit = cache.get((elements, l))
+        if hit is None or any(a is not b for a, b in zip(hit[0], src)):
+            idx = torch.tensor(list(range(l)) + [self.L], dtype=torch.int64,
+                               device=self.device)
+            for k in src:
+                if tuple(k.shape) != (self.L, 2, self.L + 1, self.n):
+                    raise ValueError(
+                        f"switching key must be [{self.L}, 2, {self.L + 1}, "
+                        f"{self.n}], got {tuple(k.shape)}")
+            keys = torch.stack([k[:l].index_select(2, idx) for k in src])
+            tabs = [self._galois_tables(g) for g in elements]
+            hit = (src, keys.contiguous(),
+                   torch.stack([t.perm32 for t in tabs]).contiguous(),
+                   torch.stack([t.perm for t in tabs]).contiguous())
+            cache[(elements, l)] = hit
+        return hit[1], hit[2], hit[3]
+
+    def _hoisted_elements(self, steps, gk, conjugate: bool):
+        """Galois element per requested output (1 for a step that is a
+        multiple of slots), checked against the exact keys in gk."""
+        steps = [int(s) for s in steps]
+        elems = [self.galois_element(s) for s in steps]
+        gk = gk or {}
+        missing = sorted({s for s, g in zip(steps, elems)
+                          if g != 1 and g not in gk})
+        if missing:
+            raise ValueError(
+                f"rotate_many needs the exact Galois key of every step (a "
+                f"composition over +-2^k keys cannot be hoisted); missing "
+                f"steps {missing} — run galois_keygen(sk, steps={missing}) "
+                f"(Pyfhel API: rotateKeyGen) first")
+        if conjugate:
+            g = self.galois_element(conjugate=True)
+            if g not in gk:
+                raise ValueError(
+                    "conjugation needs its Galois key — run galois_keygen(sk, "
+                    "conjugate=True) (Pyfhel API: rotateKeyGen) first")
+            elems.append(g)
+        return elems
+
+    def rotate_many_data(self, data: torch.Tensor, steps, gk,
+                         conjugate: bool = False) -> List[torch.Tensor]:
+        """Rotations of ct data [..., 2, l, n] by every step of `steps` from
+        ONE digit decomposition; one result per step in the order given
+        (conjugate=True appends the conjugation). Step 0 is a clone, duplicate
+        steps are computed once, any level 1..L, any batch shape. Every
+        non-zero step needs its exact key in gk. The results of one call are
+        slices of one [G, ..] allocation, which lives as long as any of them."""
+        elems = self._hoisted_elements(steps, gk, conjugate)
+        uniq = list(dict.fromkeys(g for g in elems if g != 1))
+        done: Dict[int, torch.Tensor] = {}
+        if uniq:
+            l, n = data.shape[-2], self.n
+            lead = data.shape[:-3]
+            flat = data.reshape((-1, 2, l, n))
+            R = flat.shape[0]
+            dig = self._hoist_digits(flat[:, 1], l)       # [R, l, l+1, n]
+            # the batched NTTs put one row per grid y index (<= 65535)
+            gmax = len(uniq) if self.device.type != "cuda" else max(
+                1, 65535 // (R * (l + 1)))
+            for s in range(0, len(uniq), gmax):
+                chunk = uniq[s:s + gmax]
+                out = self._rotate_hoisted(flat, dig, chunk, gk, l)
+                for j, g in enumerate(chunk):
+                    done[g] = out[j].reshape(lead + (2, l, n))
+        outs, seen = [], set()
+        for g in elems:
+            if g == 1:
+                outs.append(data.clone())
+            else:                # a repeated step gets storage of its own
+                outs.append(done[g].clone() if g in seen else done[g])
+                seen.add(g)
+        return outs
+
+    def _rotate_hoisted(self, flat: torch.Tensor, dig: torch.Tensor,
+                        elements: Sequence[int], gk, l: int) -> torch.Tensor:
+        """flat [R, 2, l, n] and its digits [R, l, l+1, n] -> the rotated
+        ciphertexts of `elements`, [G, R, 2, l, n]."""
+        keys, perm32, perm = self._galois_stack(elements, gk, l)
+        if self.device.type == "cuda":
+            be = self.backend
+            acc0, acc1 = be.ks_inner_hoisted(dig, keys, perm32,
+                                             be.level_tables(l))
+            ks0, ks1 = self._moddown_level(acc0, acc1, l)
+            return be.galois_perm_add_many(flat, ks0, ks1, perm32)
+        G, R, n = len(elements), flat.shape[0], self.n
+        idx = list(range(l)) + [self.L]
+        acc = torch.empty((2, G, R, l + 1, n), dtype=torch.int64)
+        for j in range(G):
+            dp = dig.index_select(-1, perm[j])            # sigma_g on D
+            for c in range(2):
+                for t, i in enumerate(idx):
+                    acc[c, j, :, t] = self._dot_mod(
+                        dp[:, :, t], keys[j, :, c, t], self._q(i), dim=1)
+        ks0, ks1 = self._moddown_level(acc[0], acc[1], l)
+        c0 = torch.stack([flat[:, 0].index_select(-1, perm[j])
+                          for j in range(G)])             # [G, R, l, n]
+        return torch.stack([self._modadd(c0, ks0, list(range(l))), ks1], dim=2)
+
+    def rotate_many(self, ct: Ciphertext, steps, gk,
+                    conjugate: bool = False) -> List[Ciphertext]:
+        """[rotate(ct, s) for s in steps] from one hoisted decomposition."""
+        return [Ciphertext(d, ct.scale) for d in
+                self.rotate_many_data(ct.data, steps, gk, conjugate)]
+
+    def rotate_many_tensor(self, ct: CtxtTensor, steps, gk,
+                           conjugate: bool = False) -> List[CtxtTensor]:
+        """Every ciphertext of the batch rotated by every step."""
+        return [CtxtTensor(d, ct.scale, ct.count) for d in
+                self.rotate_many_data(ct.data, steps, gk, conjugate)]
+
+    def matvec(self, M, ct, gk):
+        """M @ (slots of ct) for a real matrix M [r, c], r, c <= slots: a
+        one-shot LinearTransform (hefl/he/linear.py) at ct's level. The
+        result is at scale ct.scale * self.scale, not rescaled."""
+        from .linear import LinearTransform
+        lt = LinearTransform(self, M, level=ct.level)
+        if isinstance(ct, CtxtTensor):
+            return lt.apply_tensor(ct, gk)
+        return lt.apply(ct, gk)
 
     def modreduce_tensor_(self, ct: CtxtTensor) -> CtxtTensor:
         """Reduce lazily-summed (int64) limb values back to [0, q_i) in place

@@ -214,6 +214,16 @@ class Pyfhel:
             return self.context.rotate_tensor(ct, k, self._galois)
         return PyCtxt(self.context.rotate(ct._ct, k, self._galois), self)
 
+    def rotate_many(self, ctxt, steps):
+        """[rotate(ctxt, k) for k in steps] from one hoisted digit
+        decomposition: a list of PyCtxt (of CtxtTensor for a CtxtTensor), in
+        the order given. Every non-zero step needs its exact key —
+        rotateKeyGen(steps=steps)."""
+        if isinstance(ctxt, CtxtTensor):
+            return self.context.rotate_many_tensor(ctxt, steps, self._galois)
+        return [PyCtxt(c, self) for c in
+                self.context.rotate_many(ctxt._ct, steps, self._galois)]
+
     def conjugate(self, ct):
         """Complex-conjugate every slot of a PyCtxt or a CtxtTensor."""
         if isinstance(ct, CtxtTensor):
