@@ -40,6 +40,9 @@ def main():
     ap.add_argument("--smudge-bits", type=int, default=None, metavar="N",
                     help="threshold decryption smudging-noise width, 0..48 "
                          "(default 16)")
+    ap.add_argument("--he-packing", choices=["real", "complex"], default=None,
+                    help="'complex': two weights per CKKS slot, half the "
+                         "ciphertexts (default: real, one per slot)")
     ap.add_argument("--callbacks", action="store_true",
                     help="enable EarlyStopping/ReduceLROnPlateau per client")
     ap.add_argument("--checkpoint", default=None, metavar="PATH",
@@ -96,6 +99,9 @@ def main():
         cfg.fl.key_mode = args.key_mode
     if args.smudge_bits is not None:
         cfg.fl.smudge_bits = args.smudge_bits
+    if args.he_packing is not None:
+        import dataclasses
+        cfg.he = dataclasses.replace(cfg.he, packing=args.he_packing)
     device = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
 
     init_distributed()
@@ -149,7 +155,8 @@ def main():
         print(json.dumps({"metrics": last.metrics, "total_seconds": total,
                           "rounds": args.rounds,
                           "clients": cfg.fl.n_clients,
-                          "encrypted": cfg.fl.encrypted}))
+                          "encrypted": cfg.fl.encrypted,
+                          "he_packing": cfg.he.packing}))
     else:
         # metrics table, reference notebook cells 4-5 shape
         print("\n=== Final metrics (aggregated model, test set) ===")

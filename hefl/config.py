@@ -26,6 +26,10 @@ class HEConfig:
     sec: int = 128                      # advisory security level (API compat)
     p: int = 65537                      # accepted for Pyfhel API compat; unused by CKKS
     seed: Optional[int] = None          # deterministic keygen when set
+    # "real": one weight per slot (n/2 per ciphertext); "complex": slot j
+    # carries w[j] + i*w[j + n/2] (n per ciphertext) — exact for the C-linear
+    # FedAvg path (hefl/he/ckks.py encrypt_tensor)
+    packing: str = "real"
 
     @property
     def n(self) -> int:
@@ -35,7 +39,14 @@ class HEConfig:
     def slots(self) -> int:
         return self.m // 2
 
+    @property
+    def values_per_ct(self) -> int:
+        return self.m if self.packing == "complex" else self.m // 2
+
     def __post_init__(self):
+        if self.packing not in ("real", "complex"):
+            raise ValueError(
+                f"packing must be 'real' or 'complex', got {self.packing!r}")
         if self.m & (self.m - 1) or self.m < 16:
             raise ValueError(f"m must be a power of two >= 16, got {self.m}")
         for b in self.q_bits:

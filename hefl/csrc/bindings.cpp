@@ -70,6 +70,12 @@ torch::Tensor fft_encode(torch::Tensor vals, torch::Tensor tw_enc,
                          double scale);
 torch::Tensor fft_decode(torch::Tensor coeffs, torch::Tensor tw_dec,
                          double scale, int64_t k);
+torch::Tensor fft_encode_packed(torch::Tensor vec, int64_t count,
+                                torch::Tensor tw_enc, double scale,
+                                int64_t slots);
+torch::Tensor fft_decode_packed(torch::Tensor coeffs, torch::Tensor tw_dec,
+                                double scale, int64_t count,
+                                c10::optional<torch::Tensor> out);
 
 // cnn.hip
 torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,
@@ -218,6 +224,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "CKKS special-FFT encode: f64 slots -> int64 coeffs");
     m.def("fft_decode", &fft_decode,
           "CKKS special-FFT decode: int64 coeffs -> f32 slots");
+    m.def("fft_encode_packed", &fft_encode_packed,
+          "complex-packed encode: flat f32 vector -> int64 coeffs [B, 2*slots]",
+          py::arg("vec"), py::arg("count"), py::arg("tw_enc"),
+          py::arg("scale"), py::arg("slots"));
+    m.def("fft_decode_packed", &fft_decode_packed,
+          "complex-packed decode: int64 coeffs [B, 2*slots] -> f32 [count]",
+          py::arg("coeffs"), py::arg("tw_dec"), py::arg("scale"),
+          py::arg("count"), py::arg("out") = py::none());
     // CNN
     m.def("conv2d_fwd", &conv2d_fwd);
     m.def("conv2d_dgrad", &conv2d_dgrad);

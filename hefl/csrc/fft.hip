@@ -301,3 +301,295 @@ torch::Tensor fft_decode(torch::Tensor coeffs, torch::Tensor tw_dec,
     }
     return out;
 }
+
+// ---------------------------------------------------------------------------
+// Complex packing: a slot carries w[j] + i*w[j + slots], so one row holds
+// 2*slots real values. Encode reads the fp32 weight vector directly (row b:
+// re = vec[b*2*slots + j], im = vec[b*2*slots + slots + j], every index >=
+// count reads as 0); decode writes both halves back as fp32 and nothing at an
+// index >= count. Butterfly order, twiddle tables, LDS layout and block size
+// are those of the real-packing kernels above; the stages that do not touch
+// the load or the emit are the kernels above themselves.
+// ---------------------------------------------------------------------------
+namespace {
+
+__device__ __forceinline__ double ld_masked(const float* __restrict__ vec,
+                                            int64_t idx, int64_t count) {
+    return idx < count ? (double)vec[idx] : 0.0;
+}
+
+// ---- packed encode, slots > nblk: the FIRST global DIF stage (length =
+// slots, one group per row) fused with the masked fp32 load; writes the
+// re/im f64 scratch the later stages continue from. ----
+__global__ void fft_enc_packed_global_kernel(const float* __restrict__ vec,
+                                             int64_t count,
+                                             double* __restrict__ re,
+                                             double* __restrict__ im,
+                                             const double* __restrict__ tw,
+                                             int slots) {
+    const int lenh = slots >> 1;
+    const int64_t vbase = (int64_t)blockIdx.y * 2 * slots;
+    const int64_t base = (int64_t)blockIdx.y * slots;
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < lenh;
+         j += gridDim.x * blockDim.x) {
+        const double wr = tw[2 * j], wi = tw[2 * j + 1];
+        const double ur = ld_masked(vec, vbase + j, count);
+        const double ui = ld_masked(vec, vbase + slots + j, count);
+        const double vr = ld_masked(vec, vbase + lenh + j, count);
+        const double vi = ld_masked(vec, vbase + slots + lenh + j, count);
+        re[base + j] = ur + vr;
+        im[base + j] = ui + vi;
+        const double dr = ur - vr, di = ui - vi;
+        re[base + lenh + j] = dr * wr - di * wi;
+        im[base + lenh + j] = dr * wi + di * wr;
+    }
+}
+
+// ---- packed encode, slots <= nblk: masked fp32 load of both halves, every
+// DIF stage in LDS, bit-reverse store of the rounded coefficients. ----
+__global__ void __launch_bounds__(kFftThreads)
+fft_enc_packed_lds_kernel(const float* __restrict__ vec, int64_t count,
+                          int64_t* __restrict__ out,
+                          const double* __restrict__ tw, int slots,
+                          int log_slots, double scale) {
+    extern __shared__ double smem[];
+    double* re = smem;
+    double* im = smem + slots;
+    const int tid = threadIdx.x;
+    const int64_t vbase = (int64_t)blockIdx.y * 2 * slots;
+    for (int i = tid; i < slots; i += kFftThreads) {
+        re[i] = ld_masked(vec, vbase + i, count);
+        im[i] = ld_masked(vec, vbase + slots + i, count);
+    }
+    __syncthreads();
+    int twoff = 0;
+    const int nb2 = slots >> 1;
+    for (int length = slots; length >= 2; length >>= 1) {
+        const int lenh = length >> 1;
+        for (int p = tid; p < nb2; p += kFftThreads) {
+            const int g = p / lenh, j = p % lenh;
+            const int i0 = g * length + j;
+            const int i1 = i0 + lenh;
+            const double wr = tw[2 * (twoff + j)];
+            const double wi = tw[2 * (twoff + j) + 1];
+            const double ur = re[i0], ui = im[i0];
+            const double vr = re[i1], vi = im[i1];
+            re[i0] = ur + vr;
+            im[i0] = ui + vi;
+            const double dr = ur - vr, di = ui - vi;
+            re[i1] = dr * wr - di * wi;
+            im[i1] = dr * wi + di * wr;
+        }
+        twoff += lenh;
+        __syncthreads();
+    }
+    const double s = scale / (double)slots;
+    int64_t* orow = out + (int64_t)blockIdx.y * 2 * slots;
+    for (int i = tid; i < slots; i += kFftThreads) {
+        const unsigned dst = brev_bits((unsigned)i, log_slots);
+        orow[dst] = (int64_t)llrint(re[i] * s);
+        orow[dst + slots] = (int64_t)llrint(im[i] * s);
+    }
+}
+
+// ---- packed decode, slots <= nblk: bit-reverse gather, every DIT stage in
+// LDS, masked fp32 emit of the real and the imaginary half. ----
+__global__ void __launch_bounds__(kFftThreads)
+fft_dec_packed_lds_kernel(const int64_t* __restrict__ coeffs,
+                          float* __restrict__ out, int64_t count,
+                          const double* __restrict__ tw, int slots,
+                          int log_slots, double inv_scale) {
+    extern __shared__ double smem[];
+    double* re = smem;
+    double* im = smem + slots;
+    const int tid = threadIdx.x;
+    const int64_t* crow = coeffs + (int64_t)blockIdx.y * 2 * slots;
+    for (int i = tid; i < slots; i += kFftThreads) {
+        const unsigned src = brev_bits((unsigned)i, log_slots);
+        re[i] = (double)crow[src] * inv_scale;
+        im[i] = (double)crow[src + slots] * inv_scale;
+    }
+    __syncthreads();
+    int twoff = 0;
+    const int nb2 = slots >> 1;
+    for (int length = 2; length <= slots; length <<= 1) {
+        const int lenh = length >> 1;
+        for (int p = tid; p < nb2; p += kFftThreads) {
+            const int g = p / lenh, j = p % lenh;
+            const int i0 = g * length + j;
+            const int i1 = i0 + lenh;
+            const double wr = tw[2 * (twoff + j)];
+            const double wi = tw[2 * (twoff + j) + 1];
+            const double ur = re[i0], ui = im[i0];
+            const double tr = re[i1] * wr - im[i1] * wi;
+            const double ti = re[i1] * wi + im[i1] * wr;
+            re[i0] = ur + tr;
+            im[i0] = ui + ti;
+            re[i1] = ur - tr;
+            im[i1] = ui - ti;
+        }
+        twoff += lenh;
+        __syncthreads();
+    }
+    const int64_t obase = (int64_t)blockIdx.y * 2 * slots;
+    for (int i = tid; i < slots; i += kFftThreads) {
+        const int64_t o = obase + i;
+        if (o < count) out[o] = (float)re[i];
+        if (o + slots < count) out[o + slots] = (float)im[i];
+    }
+}
+
+// ---- packed decode, slots > nblk: the LAST global DIT stage (length =
+// slots), producing both parts, + masked fp32 emit. ----
+__global__ void fft_dec_packed_global_kernel(const double* __restrict__ re,
+                                             const double* __restrict__ im,
+                                             float* __restrict__ out,
+                                             int64_t count,
+                                             const double* __restrict__ tw,
+                                             int twoff, int slots) {
+    const int lenh = slots >> 1;
+    const int64_t base = (int64_t)blockIdx.y * slots;
+    const int64_t obase = (int64_t)blockIdx.y * 2 * slots;
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < lenh;
+         j += gridDim.x * blockDim.x) {
+        const int64_t i0 = base + j, i1 = i0 + lenh;
+        const double wr = tw[2 * (twoff + j)], wi = tw[2 * (twoff + j) + 1];
+        const double ur = re[i0], ui = im[i0];
+        const double tr = re[i1] * wr - im[i1] * wi;
+        const double ti = re[i1] * wi + im[i1] * wr;
+        const int64_t o0 = obase + j, o1 = o0 + lenh;
+        if (o0 < count) out[o0] = (float)(ur + tr);
+        if (o1 < count) out[o1] = (float)(ur - tr);
+        if (o0 + slots < count) out[o0 + slots] = (float)(ui + ti);
+        if (o1 + slots < count) out[o1 + slots] = (float)(ui - ti);
+    }
+}
+
+void check_packed_tw(const torch::Tensor& tw, int64_t slots, const char* name) {
+    TORCH_CHECK(tw.is_cuda(), name, " must be on GPU");
+    TORCH_CHECK(tw.is_contiguous() && tw.dtype() == torch::kFloat64 &&
+                    tw.numel() == 2 * (slots - 1),
+                name, " must be contiguous f64 [slots-1, 2]");
+}
+
+}  // namespace
+
+// vec: flat fp32 [>= count] -> int64 coeffs [B, 2*slots], B = ceil(count /
+// (2*slots)). tw_enc as for fft_encode.
+torch::Tensor fft_encode_packed(torch::Tensor vec, int64_t count,
+                                torch::Tensor tw_enc, double scale,
+                                int64_t slots) {
+    CHECK_CUDA_OK(vec);
+    TORCH_CHECK(vec.dtype() == torch::kFloat32, "vec must be float32");
+    TORCH_CHECK(vec.is_contiguous(), "vec must be contiguous");
+    TORCH_CHECK(slots >= 2 && slots <= (1 << 20) && (slots & (slots - 1)) == 0,
+                "slots must be a power of two in [2, 2^20]");
+    TORCH_CHECK(count >= 1, "count must be >= 1");
+    TORCH_CHECK(count <= vec.numel(), "count exceeds the vector length");
+    check_packed_tw(tw_enc, slots, "tw_enc");
+    TORCH_CHECK(tw_enc.device() == vec.device(), "tw_enc on another device");
+    const int64_t rows = (count + 2 * slots - 1) / (2 * slots);
+    TORCH_CHECK(rows <= 65535, "row count exceeds gridDim.y");
+    const int s = (int)slots;
+    const int log_slots = 31 - __builtin_clz((unsigned)s);
+    const int nblk = std::min(s, kFftNblk);
+    auto out = torch::empty({rows, 2 * slots},
+                            vec.options().dtype(torch::kInt64));
+    auto stream = at::cuda::getCurrentCUDAStream();
+    const double* tw = tw_enc.data_ptr<double>();
+    if (nblk == s) {
+        hipLaunchKernelGGL(fft_enc_packed_lds_kernel, dim3(1, (unsigned)rows),
+                           dim3(kFftThreads), 2 * nblk * sizeof(double),
+                           stream, vec.data_ptr<float>(), count,
+                           out.data_ptr<int64_t>(), tw, s, log_slots, scale);
+        return out;
+    }
+    auto re = torch::empty({rows, slots}, vec.options().dtype(torch::kFloat64));
+    auto im = torch::empty_like(re);
+    const int blocks = (int)std::min<int64_t>(
+        (s / 2 + kFftThreads - 1) / kFftThreads, 1024);
+    hipLaunchKernelGGL(fft_enc_packed_global_kernel,
+                       dim3(blocks, (unsigned)rows), dim3(kFftThreads), 0,
+                       stream, vec.data_ptr<float>(), count,
+                       re.data_ptr<double>(), im.data_ptr<double>(), tw, s);
+    int twoff = s >> 1;
+    for (int length = s >> 1; length > nblk; length >>= 1) {
+        hipLaunchKernelGGL(fft_enc_global_kernel, dim3(blocks, (unsigned)rows),
+                           dim3(kFftThreads), 0, stream,
+                           re.data_ptr<double>(), im.data_ptr<double>(), tw,
+                           twoff, s, length);
+        twoff += length >> 1;
+    }
+    hipLaunchKernelGGL(fft_enc_lds_kernel,
+                       dim3((unsigned)(s / nblk), (unsigned)rows),
+                       dim3(kFftThreads), 2 * nblk * sizeof(double), stream,
+                       nullptr, re.data_ptr<double>(), im.data_ptr<double>(),
+                       out.data_ptr<int64_t>(), tw, twoff, s, log_slots, nblk,
+                       scale);
+    return out;
+}
+
+// coeffs int64 (centered) [B, 2*slots] -> fp32 [count]: row b's real parts at
+// b*2*slots + j, imaginary parts at b*2*slots + slots + j. `out`, if given,
+// is written in place and returned.
+torch::Tensor fft_decode_packed(torch::Tensor coeffs, torch::Tensor tw_dec,
+                                double scale, int64_t count,
+                                c10::optional<torch::Tensor> out_opt) {
+    CHECK_CUDA_OK(coeffs);
+    TORCH_CHECK(coeffs.dtype() == torch::kInt64, "coeffs must be int64");
+    TORCH_CHECK(coeffs.is_contiguous(), "coeffs must be contiguous");
+    TORCH_CHECK(coeffs.dim() >= 1 && coeffs.size(-1) >= 4 &&
+                    coeffs.size(-1) % 2 == 0,
+                "coeffs must be [.., 2*slots]");
+    const int64_t slots = coeffs.size(-1) / 2;
+    TORCH_CHECK((slots & (slots - 1)) == 0 && slots <= 2 * kFftNblk,
+                "slots must be a power of two <= ", 2 * kFftNblk);
+    const int64_t rows = coeffs.numel() / (2 * slots);
+    TORCH_CHECK(rows <= 65535, "row count exceeds gridDim.y");
+    TORCH_CHECK(count >= 1, "count must be >= 1");
+    TORCH_CHECK(count <= rows * 2 * slots, "count exceeds B * 2 * slots");
+    check_packed_tw(tw_dec, slots, "tw_dec");
+    TORCH_CHECK(tw_dec.device() == coeffs.device(), "tw_dec on another device");
+    torch::Tensor out;
+    if (out_opt.has_value()) {
+        out = *out_opt;
+        CHECK_CUDA_OK(out);
+        TORCH_CHECK(out.device() == coeffs.device(), "out on another device");
+        TORCH_CHECK(out.dtype() == torch::kFloat32, "out must be float32");
+        TORCH_CHECK(out.is_contiguous(), "out must be contiguous");
+        TORCH_CHECK(out.numel() == count, "out must hold exactly count values");
+    } else {
+        out = torch::empty({count}, coeffs.options().dtype(torch::kFloat32));
+    }
+    const int s = (int)slots;
+    const int log_slots = 31 - __builtin_clz((unsigned)s);
+    const int nblk = std::min(s, kFftNblk);
+    auto stream = at::cuda::getCurrentCUDAStream();
+    const double* tw = tw_dec.data_ptr<double>();
+    const double inv_scale = 1.0 / scale;
+    if (nblk == s) {
+        hipLaunchKernelGGL(fft_dec_packed_lds_kernel, dim3(1, (unsigned)rows),
+                           dim3(kFftThreads), 2 * nblk * sizeof(double),
+                           stream, coeffs.data_ptr<int64_t>(),
+                           out.data_ptr<float>(), count, tw, s, log_slots,
+                           inv_scale);
+        return out;
+    }
+    // slots == 2 * nblk: stages up to nblk in LDS, the last one global
+    auto re = torch::empty({rows, slots},
+                           coeffs.options().dtype(torch::kFloat64));
+    auto im = torch::empty_like(re);
+    hipLaunchKernelGGL(fft_dec_lds_kernel,
+                       dim3((unsigned)(s / nblk), (unsigned)rows),
+                       dim3(kFftThreads), 2 * nblk * sizeof(double), stream,
+                       coeffs.data_ptr<int64_t>(), re.data_ptr<double>(),
+                       im.data_ptr<double>(), nullptr, tw, s, log_slots, nblk,
+                       inv_scale, 0);
+    const int blocks = (int)std::min<int64_t>(
+        (s / 2 + kFftThreads - 1) / kFftThreads, 1024);
+    hipLaunchKernelGGL(fft_dec_packed_global_kernel,
+                       dim3(blocks, (unsigned)rows), dim3(kFftThreads), 0,
+                       stream, re.data_ptr<double>(), im.data_ptr<double>(),
+                       out.data_ptr<float>(), count, tw, nblk - 1, s);
+    return out;
+}

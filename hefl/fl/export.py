@@ -34,6 +34,7 @@ def encrypt_model_weights(he: Pyfhel, model: torch.nn.Module) -> Dict[str, dict]
             "data": ct.data.cpu(),
             "scale": ct.scale,
             "count": ct.count,
+            "packing": ct.packing,
             "shape": tuple(p.shape),
         }
     print("Time to encrypt weights:", time.time() - start)
@@ -78,7 +79,9 @@ def import_encrypted_weights(file_name: str, device: str = "cpu"):
     he.from_bytes_publicKey(payload["key"]["public_key"])
     val = {}
     for name, d in payload["val"].items():
-        val[name] = CtxtTensor(d["data"].to(device), d["scale"], d["count"])
+        # a dict written before complex packing existed has no "packing"
+        val[name] = CtxtTensor(d["data"].to(device), d["scale"], d["count"],
+                               d.get("packing", "real"))
     print("Time to import:", time.time() - start)
     return he, val
 
@@ -91,7 +94,7 @@ def decrypt_into_model(he: Pyfhel, val: Dict[str, CtxtTensor],
         for i, p in enumerate(model.parameters()):
             d = val[f"c_{i}_0"]
             ct = d if isinstance(d, CtxtTensor) else CtxtTensor(
-                d["data"], d["scale"], d["count"])
+                d["data"], d["scale"], d["count"], d.get("packing", "real"))
             vec = he.decrypt_tensor(ct)
             p.copy_(vec.reshape(p.shape).to(p.dtype))
     print("Time to decrypt:", time.time() - start)

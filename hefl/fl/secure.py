@@ -5,7 +5,9 @@ This collapses the reference's whole aggregation stack — pickle export
 add/mult loop (:366-390, timed at 231 s for 2 clients) — into:
 
   1. encrypt the client's flat fp32 weight vector into slot-packed CKKS
-     ciphertexts resident in HBM (one [B, 2, L, n] int64 tensor), in SLABS,
+     ciphertexts resident in HBM (one [B, 2, L, n] int64 tensor), in SLABS
+     (n/2 weights per ciphertext, or n with he.packing="complex": every
+     step below is C-linear in the slots, so both parts of a slot average),
   2. per slab, ONE async all-reduce(SUM) on the raw RNS coefficients,
      issued as soon as that slab is encrypted — the collective for slab i
      rides the 7 xGMI links while slab i+1 is still encrypting on the
@@ -215,7 +217,9 @@ class SecureAggregator:
             from ..he.ckks import Ciphertext
             prod = self.ctx.mul_ct(Ciphertext(ct.data, ct.scale),
                                    self.enc_denom, self.keys.relin)
-            out = CtxtTensor(prod.data, prod.scale, ct.count)
+            # the encrypted 1/n is a real constant in every slot, so the
+            # product keeps whatever packing ct has
+            out = CtxtTensor(prod.data, prod.scale, ct.count, ct.packing)
             return self.ctx.rescale_tensor(out)
         return self.ctx.rescale_tensor(
             self.ctx.mul_scalar_tensor(ct, 1.0 / n))
@@ -249,9 +253,9 @@ class SecureAggregator:
         n = n_clients if n_clients is not None else world
         assert n <= 8, "lazy int64 reduction is proven for <= 8 summands"
         ctx = self.ctx
-        slots = ctx.slots
+        per_ct = ctx.values_per_ct     # slots, or n under complex packing
         count = vec.numel()
-        B = (count + slots - 1) // slots
+        B = (count + per_ct - 1) // per_ct
         slab = self._slab_cts()
         if world <= 1 or B <= slab:
             ct = self.encrypt(vec)
@@ -259,20 +263,20 @@ class SecureAggregator:
         data = torch.empty((B, 2, ctx.L, ctx.n), dtype=torch.int64,
                            device=ctx.device)
         works = []
-        scale = None
+        scale, packing = None, "real"
         for b0 in range(0, B, slab):
             b1 = min(B, b0 + slab)
-            sub = vec[b0 * slots: min(count, b1 * slots)]
+            sub = vec[b0 * per_ct: min(count, b1 * per_ct)]
             ct_slab = ctx.encrypt_tensor(sub, self.keys.pk)
             data[b0:b1].copy_(ct_slab.data)
-            scale = ct_slab.scale
+            scale, packing = ct_slab.scale, ct_slab.packing
             works.append(dist.all_reduce(data[b0:b1], op=dist.ReduceOp.SUM,
                                          async_op=True))
         self._t("encrypt weights", t0)
         t1 = time.perf_counter()
         for w in works:
             w.wait()
-        ct = CtxtTensor(data, scale, count)
+        ct = CtxtTensor(data, scale, count, packing)
         self.ctx.modreduce_tensor_(ct)
         out = self._divide(ct, n)
         self._t("aggregate", t1)
@@ -303,7 +307,8 @@ class SecureAggregator:
                      for i in range(0, share.shape[0], slab)]
             for w in works:
                 w.wait()
-        return self.ctx.combine_shares_tensor(share, ct.scale, ct.count)
+        return self.ctx.combine_shares_tensor(share, ct.scale, ct.count,
+                                              packing=ct.packing)
 
     def fedavg(self, vec: torch.Tensor, n_clients: Optional[int] = None) -> torch.Tensor:
         """Full encrypted FedAvg of a flat fp32 weight vector."""

@@ -141,7 +141,7 @@ class SequentialFL:
                 self.ctx.reseed(i)
                 ct = self.ctx.encrypt_tensor(v, self.keys.pk)
                 agg = ct if agg is None else CtxtTensor(
-                    agg.data + ct.data, agg.scale, agg.count)
+                    agg.data + ct.data, agg.scale, agg.count, agg.packing)
             self.ctx.modreduce_tensor_(agg)
             avg = self.ctx.rescale_tensor(self.ctx.mul_scalar_tensor(agg, 1.0 / n))
             if self.key_shares is not None:
@@ -153,7 +153,8 @@ class SequentialFL:
                         avg, ks.sk_share, self.cfg.fl.smudge_bits, lead=i == 0)
                     acc = h if acc is None else acc.add_(h)
                 new_g = self.ctx.combine_shares_tensor(
-                    acc, avg.scale, avg.count).to(self.device)
+                    acc, avg.scale, avg.count,
+                    packing=avg.packing).to(self.device)
             else:
                 new_g = self.ctx.decrypt_tensor(avg, self.keys.sk).to(self.device)
         else:

@@ -350,6 +350,10 @@ class CtxtTensor:
     data: torch.Tensor
     scale: float
     count: int  # number of packed real values
+    # "real": ciphertext b holds values [b*slots, (b+1)*slots) in its real
+    # parts; "complex": values [b*n, b*n + slots) in the real parts and
+    # [b*n + slots, (b+1)*n) in the imaginary parts of the same slots
+    packing: str = "real"
 
     @property
     def level(self) -> int:
@@ -395,6 +399,10 @@ class CKKSContext:
         self.cfg = cfg
         self.n = cfg.m
         self.slots = cfg.m // 2
+        # slot packing of encrypt_tensor and the real values one of its
+        # ciphertexts carries: slots, or n under "complex"
+        self.packing = cfg.packing
+        self.values_per_ct = cfg.values_per_ct
         # chain primes + ONE special prime for hybrid key-switching (the
         # relinearization path, configs #3/#5); special prime is never part
         # of a ciphertext level, only of relin keys.
@@ -582,17 +590,32 @@ class CKKSContext:
     # ----- encode / decode -----
     def encode(self, vals: np.ndarray, nlimbs: Optional[int] = None,
                scale: Optional[float] = None) -> Plaintext:
-        """vals: real [..., k<=slots] -> NTT-form RNS plaintext."""
+        """vals: real or complex [..., k<=slots] -> NTT-form RNS plaintext.
+        A complex input fills both parts of each slot (on the GPU its parts
+        are taken as fp32, the packed kernel's input format)."""
         scale = self.scale if scale is None else scale
         nlimbs = self.L if nlimbs is None else nlimbs
+        cplx = (vals.is_complex() if torch.is_tensor(vals)
+                else np.iscomplexobj(vals))
         if self.device.type == "cuda":
             # full-device path: special FFT + rounding on the GPU, then one
             # fused multi-limb remainder + NTT
+            if cplx:
+                vt = vals if torch.is_tensor(vals) else torch.from_numpy(
+                    np.asarray(vals, dtype=np.complex128))
+                ct = self.encoder.encode_complex_torch(vt.to(self.device), scale)
+                return Plaintext(self._to_rns_ntt(ct, nlimbs), scale)
             vt = (vals if torch.is_tensor(vals)
                   else torch.from_numpy(np.asarray(vals, dtype=np.float64)))
             ct = self.encoder.encode_torch(vt.to(self.device), scale)
             return Plaintext(self._to_rns_ntt(ct, nlimbs), scale)
-        coeffs = self.encoder.encode(np.asarray(vals, dtype=np.float64), scale)
+        if cplx:
+            if torch.is_tensor(vals):
+                vals = vals.cpu().numpy()
+            coeffs = self.encoder.encode_complex(vals, scale)
+        else:
+            coeffs = self.encoder.encode(np.asarray(vals, dtype=np.float64),
+                                         scale)
         out = []
         if coeffs.dtype == np.int64:
             # fast path: one upload, per-limb remainder + NTT on device
@@ -607,7 +630,63 @@ class CKKSContext:
                 out.append(self.backend.ntt(ci_t, i))
         return Plaintext(torch.stack(out, dim=-2), scale)
 
-    def decode(self, pt: Plaintext, k: int) -> np.ndarray:
+    def _centered_coeffs(self, data: torch.Tensor):
+        """NTT-form plaintext [..., L', n] -> its centered integer
+        coefficients [..., n], by the three branches of decode: an int64
+        tensor on the context device where limb 0 alone determines them,
+        else a numpy object array (big-int CRT). Only the complex paths come
+        through here; decode keeps its own statements for real values."""
+        nlimbs = data.shape[-2]
+        if nlimbs == 1:
+            # fast path (the FedAvg pipeline decrypts at level 1): center on
+            # device, f64 is exact for plaintext magnitudes << 2^53
+            q = self._q(0)
+            c = self.backend.ntt(data[..., 0, :], 0, inverse=True)
+            return torch.where(c > q // 2, c - q, c)
+        # multi-limb fast path: when the plaintext magnitude is << q0/2 (true
+        # for any decode of real-valued weights at scale <= 2^45), the
+        # centered limb-0 residue IS the integer value — checked against
+        # limb 1 on a sample, falling back to exact big-int CRT on mismatch.
+        q0 = self._q(0)
+        c0 = self.backend.ntt(data[..., 0, :], 0, inverse=True)
+        cent0 = torch.where(c0 > q0 // 2, c0 - q0, c0)
+        if cent0.abs().max().item() < q0 // 4:
+            q1 = self._q(1)
+            c1 = self.backend.ntt(data[..., 1, :], 1, inverse=True)
+            cent1 = torch.where(c1 > q1 // 2, c1 - q1, c1)
+            if torch.equal(torch.remainder(cent0, q1), torch.remainder(cent1, q1)):
+                return cent0
+        # exact big-int CRT path (plaintext too large for limb-0 shortcut)
+        coeff_limbs = []
+        for i in range(nlimbs):
+            c = self.backend.ntt(data[..., i, :], i, inverse=True)
+            coeff_limbs.append(c.cpu().numpy().astype(object))
+        qs = [self._q(i) for i in range(nlimbs)]
+        Q = math.prod(qs)
+        x = 0
+        for i, q in enumerate(qs):
+            Qi = Q // q
+            hi = pow(Qi % q, -1, q)
+            x = x + coeff_limbs[i] * ((Qi * hi) % Q)
+        x = np.mod(x, Q)
+        return np.where(x > Q // 2, x - Q, x)
+
+    def _decode_complex(self, pt: Plaintext, k: int):
+        """decode's three branches (one limb, limb-0 shortcut, big-int CRT)
+        for complex slot values."""
+        cent = self._centered_coeffs(pt.data)
+        if torch.is_tensor(cent):
+            if self.device.type == "cuda":
+                return self.encoder.decode_complex_torch(cent, pt.scale, k)
+            cent = cent.cpu().numpy()
+        return self.encoder.decode_complex(cent, pt.scale, k)
+
+    def decode(self, pt: Plaintext, k: int, complex: bool = False):
+        """First k slot values of a plaintext: their real parts, or with
+        complex=True the complex values. A tensor on a GPU context (fp32 /
+        complex64), a numpy array on the CPU."""
+        if complex:
+            return self._decode_complex(pt, k)
         data = pt.data
         nlimbs = data.shape[-2]
         if nlimbs == 1:
@@ -830,8 +909,29 @@ class CKKSContext:
 
     # ----- batched tensor API (flat weight vectors) -----
     def encrypt_tensor(self, vec: torch.Tensor, pk: torch.Tensor) -> CtxtTensor:
-        """Slot-pack a flat fp32 vector into ceil(len/slots) ciphertexts."""
+        """Pack a flat fp32 vector into ceil(len / values_per_ct) ciphertexts:
+        one value per slot, or with cfg.packing == "complex" two (slot j of
+        ciphertext b carries vec[b*n + j] + i*vec[b*n + slots + j]). The
+        real-packing statements below, and those of decrypt_tensor and decode,
+        are kept as they were before the option existed: the host-side
+        sequence between training rounds was once seen not to be neutral for
+        the training's atomics-order noise (PERFORMANCE.md)."""
         count = vec.numel()
+        if self.packing == "complex":
+            if count < 1:
+                raise ValueError("cannot encrypt an empty vector")
+            if self.device.type == "cuda":
+                # one HIP launch set straight from the fp32 weights: no f64
+                # staging buffer, no slice copy, no cast
+                coeffs = self.encoder.encode_packed_torch(
+                    vec.detach().reshape(-1).to(self.device, torch.float32),
+                    self.scale)
+                pt = Plaintext(self._to_rns_ntt(coeffs), self.scale)
+            else:
+                pt = self.encode(self.encoder.pack_complex(
+                    vec.detach().float().cpu().numpy()))
+            data = self._encrypt_data(pt.data, pk)
+            return CtxtTensor(data, pt.scale, count, "complex")
         B = (count + self.slots - 1) // self.slots
         if self.device.type == "cuda":
             buf = torch.zeros(B * self.slots, dtype=torch.float64,
@@ -847,19 +947,38 @@ class CKKSContext:
 
     def decrypt_tensor(self, ct: CtxtTensor, sk: torch.Tensor) -> torch.Tensor:
         pt = self._decrypt_data(ct.data, sk)      # [B, L, n]
+        if ct.packing != "real":
+            return self._decode_tensor(pt, ct.scale, ct.count, ct.packing)
         vals = self.decode(Plaintext(pt, ct.scale), self.slots)  # [B, slots]
         if torch.is_tensor(vals):
             return vals.reshape(-1)[:ct.count].to(torch.float32)
         flat = torch.from_numpy(np.ascontiguousarray(vals.reshape(-1)[:ct.count]))
         return flat.to(torch.float32)
 
-    def _decode_tensor(self, pt: torch.Tensor, scale: float,
-                       count: int) -> torch.Tensor:
+    def _decode_tensor(self, pt: torch.Tensor, scale: float, count: int,
+                       packing: str = "real") -> torch.Tensor:
+        if packing != "real":
+            if packing != "complex":
+                raise ValueError(f"unknown packing {packing!r}")
+            return self._decode_packed(pt, scale, count)
         vals = self.decode(Plaintext(pt, scale), self.slots)  # [B, slots]
         if torch.is_tensor(vals):
             return vals.reshape(-1)[:count].to(torch.float32)
         flat = torch.from_numpy(np.ascontiguousarray(vals.reshape(-1)[:count]))
         return flat.to(torch.float32)
+
+    def _decode_packed(self, pt: torch.Tensor, scale: float,
+                       count: int) -> torch.Tensor:
+        """Complex-packed plaintexts [B, L', n] -> the fp32 vector [count]."""
+        if count > pt.shape[0] * self.n:
+            raise ValueError(f"{pt.shape[0]} ciphertexts hold at most "
+                             f"{pt.shape[0] * self.n} values, count is {count}")
+        cent = self._centered_coeffs(pt)
+        if torch.is_tensor(cent):
+            return self.encoder.decode_packed_torch(cent, scale, count)
+        z = self.encoder.decode_complex(cent, scale, self.slots)
+        flat = self.encoder.unpack_complex(z, count)
+        return torch.from_numpy(np.ascontiguousarray(flat)).to(torch.float32)
 
     def partial_decrypt_tensor(self, ct: CtxtTensor, sk_share: torch.Tensor,
                                smudge_bits: int, lead: bool,
@@ -870,27 +989,33 @@ class CKKSContext:
                                          bits=bits)
 
     def combine_shares_tensor(self, share_sum_lazy: torch.Tensor, scale: float,
-                              count: int) -> torch.Tensor:
+                              count: int, *, packing: str = "real") -> torch.Tensor:
         """Lazy int64 SUM of <= 8 parties' shares [B, Lc, n] -> fp32 vector.
         Each share is < q < 2^60, so the sum is < 2^63 and the modreduce
-        conditional-subtract chain applies. Reduces the sum in place."""
+        conditional-subtract chain applies. Reduces the sum in place.
+        `packing` is that of the ciphertext the shares were taken of."""
         pt = self._modreduce_(share_sum_lazy)
-        return self._decode_tensor(pt, scale, count)
+        return self._decode_tensor(pt, scale, count, packing)
 
     def add_tensor(self, a: CtxtTensor, b: CtxtTensor) -> CtxtTensor:
         assert a.count == b.count and a.level == b.level
+        if a.packing != b.packing:
+            raise ValueError(
+                f"cannot add a {a.packing}-packed and a {b.packing}-packed "
+                f"tensor: their slots hold different values")
         self._check_add_scales(a.scale, b.scale)
         limbs = list(range(a.level))
         return CtxtTensor(self._modadd(a.data, b.data, limbs),
-                          max(a.scale, b.scale), a.count)
+                          max(a.scale, b.scale), a.count, a.packing)
 
     def mul_scalar_tensor(self, ct: CtxtTensor, x: float) -> CtxtTensor:
         return CtxtTensor(self.mul_scalar_data(ct.data, x),
-                          ct.scale * self.scale, ct.count)
+                          ct.scale * self.scale, ct.count, ct.packing)
 
     def rescale_tensor(self, ct: CtxtTensor) -> CtxtTensor:
         return CtxtTensor(self.rescale_data(ct.data),
-                          ct.scale / float(self._q(ct.level - 1)), ct.count)
+                          ct.scale / float(self._q(ct.level - 1)), ct.count,
+                          ct.packing)
 
     # ----- relinearization (ct x ct support; reference intent at
     # FLPyfhelin.py:357-364 gen_rekey — dead code there, real here) -----
@@ -1343,17 +1468,24 @@ class CKKSContext:
     def sum_slots(self, ct: Ciphertext, gk, width: int) -> Ciphertext:
         return Ciphertext(self.sum_slots_data(ct.data, gk, width), ct.scale)
 
+    # On a complex-packed tensor the slot operations act on both halves of
+    # every ciphertext at once, because they are C-linear in the slots (or,
+    # for conjugation, act on the imaginary part alone): a rotation by r
+    # rolls values [b*n, b*n + slots) and [b*n + slots, (b+1)*n) by r each,
+    # sum_slots sums each half, a real LinearTransform maps each half, and
+    # conjugate negates the second half.
     def rotate_tensor(self, ct: CtxtTensor, step: int, gk) -> CtxtTensor:
         """Rotate every ciphertext of the batch by the same step."""
         return CtxtTensor(self.rotate_data(ct.data, step, gk), ct.scale,
-                          ct.count)
+                          ct.count, ct.packing)
 
     def conjugate_tensor(self, ct: CtxtTensor, gk) -> CtxtTensor:
-        return CtxtTensor(self.conjugate_data(ct.data, gk), ct.scale, ct.count)
+        return CtxtTensor(self.conjugate_data(ct.data, gk), ct.scale, ct.count,
+                          ct.packing)
 
     def sum_slots_tensor(self, ct: CtxtTensor, gk, width: int) -> CtxtTensor:
         return CtxtTensor(self.sum_slots_data(ct.data, gk, width), ct.scale,
-                          ct.count)
+                          ct.count, ct.packing)
 
     # ----- hoisted multi-step rotations -----
     # Everything of a rotation's key-switch up to and including the digit
@@ -1513,7 +1645,7 @@ class CKKSContext:
     def rotate_many_tensor(self, ct: CtxtTensor, steps, gk,
                            conjugate: bool = False) -> List[CtxtTensor]:
         """Every ciphertext of the batch rotated by every step."""
-        return [CtxtTensor(d, ct.scale, ct.count) for d in
+        return [CtxtTensor(d, ct.scale, ct.count, ct.packing) for d in
                 self.rotate_many_data(ct.data, steps, gk, conjugate)]
 
     def matvec(self, M, ct, gk):

@@ -80,7 +80,11 @@ class Encoder:
         if pad:
             vals = np.concatenate(
                 [vals, np.zeros(vals.shape[:-1] + (pad,))], axis=-1)
-        z = self.fft_special_inv(vals)
+        return self._round_coeffs(self.fft_special_inv(vals), scale)
+
+    @staticmethod
+    def _round_coeffs(z: np.ndarray, scale: float) -> np.ndarray:
+        """Coefficient-side complex values -> rounded [re | im] integers."""
         re = np.round(z.real * scale)
         im = np.round(z.imag * scale)
         peak = max(np.abs(re).max(initial=0.0), np.abs(im).max(initial=0.0))
@@ -95,12 +99,49 @@ class Encoder:
 
     def decode(self, coeffs: np.ndarray, scale: float, k: int) -> np.ndarray:
         """Centered integer coeffs [..., n] -> real slot values [..., k]."""
+        return self.decode_complex(coeffs, scale, k).real
+
+    # --- complex slots: the full C^{n/2} embedding. encode / decode above
+    # are its restriction to real slot values. ---
+    def encode_complex(self, vals: np.ndarray, scale: float) -> np.ndarray:
+        """vals: complex [..., k<=slots] -> integer coeffs [..., n], with
+        encode's layout and int64/object overflow guard."""
+        vals = np.asarray(vals, dtype=np.complex128)
+        pad = self.slots - vals.shape[-1]
+        if pad < 0:
+            raise ValueError("too many values for slot count")
+        if pad:
+            vals = np.concatenate(
+                [vals, np.zeros(vals.shape[:-1] + (pad,), dtype=np.complex128)],
+                axis=-1)
+        return self._round_coeffs(self.fft_special_inv(vals), scale)
+
+    def decode_complex(self, coeffs: np.ndarray, scale: float,
+                       k: int) -> np.ndarray:
+        """Centered integer coeffs [..., n] -> complex slot values [..., k]."""
         c = np.asarray(coeffs)
         half = self.slots
         cf = c.astype(np.float64)
         z = cf[..., :half] + 1j * cf[..., half:]
         v = self.fft_special(z / scale)
-        return v.real[..., :k]
+        return v[..., :k]
+
+    # --- complex packing of a flat real vector: row b carries
+    # vec[b*n + j] + i * vec[b*n + slots + j], zero past the end ---
+    def pack_complex(self, vec: np.ndarray) -> np.ndarray:
+        """Flat real [count] -> complex [ceil(count / n), slots]."""
+        vec = np.asarray(vec, dtype=np.float64).reshape(-1)
+        B = max(1, -(-vec.shape[0] // self.n))
+        buf = np.zeros(B * self.n, dtype=np.float64)
+        buf[:vec.shape[0]] = vec
+        buf = buf.reshape(B, 2, self.slots)
+        return buf[:, 0] + 1j * buf[:, 1]
+
+    def unpack_complex(self, z: np.ndarray, count: int) -> np.ndarray:
+        """Complex [B, slots] -> the flat real [count] pack_complex packed."""
+        z = np.asarray(z)
+        flat = np.stack([z.real, z.imag], axis=-2).reshape(-1)
+        return flat[:count]
 
 
 # ---------------------------------------------------------------------------
@@ -252,9 +293,93 @@ class TorchEncoderMixin:
         v = self.fft_special_torch(z)
         return v.real[..., :k].to(_torch.float32)
 
+    # ----- complex slots / complex packing -----
+    def encode_complex_torch(self, vals: "_torch.Tensor",
+                             scale: float) -> "_torch.Tensor":
+        """vals: complex [..., k<=slots] -> int64 coeffs [..., n]. On the GPU
+        the values go through the packed HIP kernel, which takes fp32 pairs:
+        real and imaginary parts are rounded to fp32 on the way in."""
+        pad = self.slots - vals.shape[-1]
+        if pad < 0:
+            raise ValueError("too many values for slot count")
+        if vals.is_cuda:
+            lead = vals.shape[:-1]
+            v = _torch.view_as_real(vals.reshape(-1, vals.shape[-1])
+                                    .to(_torch.complex64))     # [R, k, 2]
+            rows = _torch.nn.functional.pad(v.transpose(1, 2), (0, pad))
+            coeffs = self.encode_packed_torch(rows.reshape(-1), scale)
+            return coeffs.reshape(*lead, self.n)
+        vals = vals.to(_torch.complex128)
+        if pad:
+            vals = _torch.nn.functional.pad(vals, (0, pad))
+        z = self.fft_special_inv_torch(vals)
+        re = _torch.round(z.real * scale)
+        im = _torch.round(z.imag * scale)
+        peak = max(re.abs().max().item(), im.abs().max().item())
+        if peak >= 2.0 ** 52:
+            raise OverflowError("encode overflow: scale too large for f64 path")
+        return _torch.cat([re, im], dim=-1).to(_torch.int64)
+
+    def decode_complex_torch(self, coeffs: "_torch.Tensor", scale: float,
+                             k: int) -> "_torch.Tensor":
+        """Centered int64 coeffs [..., n] -> complex [..., k]: complex64 from
+        the packed HIP kernel on the GPU, complex128 on the CPU."""
+        if coeffs.is_cuda:
+            lead = coeffs.shape[:-1]
+            flat = coeffs.reshape(-1, self.n)
+            v = self.decode_packed_torch(flat, scale, flat.numel())
+            v = v.reshape(-1, 2, self.slots)
+            return _torch.complex(v[:, 0], v[:, 1]).reshape(
+                *lead, self.slots)[..., :k]
+        half = self.slots
+        cf = coeffs.to(_torch.float64)
+        z = _torch.complex(cf[..., :half], cf[..., half:]) / scale
+        return self.fft_special_torch(z)[..., :k]
+
+    def encode_packed_torch(self, vec: "_torch.Tensor",
+                            scale: float) -> "_torch.Tensor":
+        """Flat real vector [count] -> int64 coeffs [ceil(count / n), n], slot
+        j of row b carrying vec[b*n + j] + i*vec[b*n + slots + j]. On the GPU
+        one HIP launch set reads the vector as fp32; on the CPU it is the
+        numpy oracle."""
+        vec = vec.reshape(-1)
+        if vec.is_cuda:
+            import hefl
+            tw_enc, _ = self._hip_tables(vec.device)
+            return hefl.load_extension().fft_encode_packed(
+                vec.to(_torch.float32).contiguous(), vec.numel(), tw_enc,
+                float(scale), self.slots)
+        coeffs = self.encode_complex(
+            self.pack_complex(vec.detach().double().numpy()), scale)
+        if coeffs.dtype != np.int64:
+            raise OverflowError("encode overflow: scale too large for f64 path")
+        return _torch.from_numpy(np.ascontiguousarray(coeffs))
+
+    def decode_packed_torch(self, coeffs: "_torch.Tensor", scale: float,
+                            count: int, out=None) -> "_torch.Tensor":
+        """Centered int64 coeffs [B, n] -> the fp32 vector [count] that
+        encode_packed_torch packed. `out` (fp32 [count], contiguous, on the
+        coefficients' device) is written in place and returned."""
+        if coeffs.is_cuda:
+            import hefl
+            _, tw_dec = self._hip_tables(coeffs.device)
+            return hefl.load_extension().fft_decode_packed(
+                coeffs.contiguous(), tw_dec, float(scale), int(count), out)
+        z = self.decode_complex(coeffs.numpy(), scale, self.slots)
+        flat = _torch.from_numpy(np.ascontiguousarray(
+            self.unpack_complex(z.reshape(-1, self.slots), count))
+        ).to(_torch.float32)
+        if out is None:
+            return flat
+        if out.shape != flat.shape or out.dtype != _torch.float32:
+            raise ValueError("out must be fp32 with exactly count elements")
+        return out.copy_(flat)
+
 
 # graft the torch methods onto Encoder (mixin-by-assignment; __bases__
 # reassignment is not allowed on classes deriving from object directly)
 for _name in ("_torch_tables", "_hip_tables", "fft_special_torch",
-              "fft_special_inv_torch", "encode_torch", "decode_torch"):
+              "fft_special_inv_torch", "encode_torch", "decode_torch",
+              "encode_complex_torch", "decode_complex_torch",
+              "encode_packed_torch", "decode_packed_torch"):
     setattr(Encoder, _name, getattr(TorchEncoderMixin, _name))

@@ -194,6 +194,7 @@ class LinearTransform:
         return Ciphertext(self.apply_data(ct.data, gk), ct.scale * self.scale)
 
     def apply_tensor(self, ct: CtxtTensor, gk) -> CtxtTensor:
-        """Every ciphertext (vector) of the batch through the one matrix."""
+        """Every ciphertext (vector) of the batch through the one matrix; on
+        a complex-packed tensor, both halves of every ciphertext."""
         return CtxtTensor(self.apply_data(ct.data, gk), ct.scale * self.scale,
-                          ct.count)
+                          ct.count, ct.packing)

@@ -29,25 +29,43 @@ from .ckks import CKKSContext, Ciphertext, CtxtTensor, KeyPair
 
 _MAGIC = b"HEFL"
 _VERSION = 1
+# Version 2 appends one byte after the q_bits: the slot packing. A context
+# with real packing is still written as version 1, byte for byte what it
+# always was, so a stream without the field reads as "real".
+_VERSION_PACKING = 2
+_PACKINGS = ("real", "complex")
 
 
 def _pack_header(kind: bytes, cfg: HEConfig) -> bytes:
-    return _MAGIC + struct.pack(
-        "<H4sIIIH", _VERSION, kind, cfg.m, cfg.scale_bits, cfg.sec,
+    ver = _VERSION if cfg.packing == "real" else _VERSION_PACKING
+    head = _MAGIC + struct.pack(
+        "<H4sIIIH", ver, kind, cfg.m, cfg.scale_bits, cfg.sec,
         len(cfg.q_bits)) + struct.pack(f"<{len(cfg.q_bits)}I", *cfg.q_bits)
+    if ver == _VERSION_PACKING:
+        head += struct.pack("<B", _PACKINGS.index(cfg.packing))
+    return head
 
 
 def _unpack_header(buf: bytes, expect: bytes):
     if buf[:4] != _MAGIC:
         raise ValueError("not a hefl HE byte stream")
     ver, kind, m, scale_bits, sec, nq = struct.unpack("<H4sIIIH", buf[4:24])
-    if ver != _VERSION:
+    if ver not in (_VERSION, _VERSION_PACKING):
         raise ValueError(f"unsupported version {ver}")
     if kind != expect:
         raise ValueError(f"expected {expect!r} stream, got {kind!r}")
     q_bits = struct.unpack(f"<{nq}I", buf[24:24 + 4 * nq])
-    cfg = HEConfig(m=m, scale_bits=scale_bits, sec=sec, q_bits=tuple(q_bits))
-    return cfg, 24 + 4 * nq
+    off = 24 + 4 * nq
+    packing = "real"
+    if ver == _VERSION_PACKING:
+        (code,) = struct.unpack("<B", buf[off:off + 1])
+        if code >= len(_PACKINGS):
+            raise ValueError(f"unknown packing code {code}")
+        packing = _PACKINGS[code]
+        off += 1
+    cfg = HEConfig(m=m, scale_bits=scale_bits, sec=sec, q_bits=tuple(q_bits),
+                   packing=packing)
+    return cfg, off
 
 
 class PyCtxt:
@@ -144,9 +162,12 @@ class Pyfhel:
     def contextGen(self, p: int = 65537, m: int = 2048, sec: int = 128,
                    base: int = 2, flagBatching: bool = False,
                    scale_bits: int = 40, q_bits=(60, 40),
-                   seed: Optional[int] = None, device: str = "cpu"):
+                   seed: Optional[int] = None, device: str = "cpu",
+                   packing: str = "real"):
+        """packing="complex" makes encrypt_tensor put two values in each
+        slot; encryptFrac / decryptFrac stay one real scalar either way."""
         cfg = HEConfig(m=m, scale_bits=scale_bits, q_bits=tuple(q_bits),
-                       sec=sec, p=p, seed=seed)
+                       sec=sec, p=p, seed=seed, packing=packing)
         self.contextGen_cfg(cfg, device=device)
 
     def contextGen_cfg(self, cfg: HEConfig, device: str = "cpu"):
