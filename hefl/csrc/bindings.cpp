@@ -162,6 +162,13 @@ std::vector<torch::Tensor> conv_bwd_pair(torch::Tensor dy, torch::Tensor w,
                                          torch::Tensor x, int64_t R,
                                          int64_t S, int64_t pad, int64_t H,
                                          int64_t W, int64_t gkey);
+bool conv1_pool_bwd_ok(torch::Tensor dy, torch::Tensor x, int64_t R,
+                       int64_t S, int64_t pad, int64_t convH, int64_t convW);
+std::vector<torch::Tensor> conv1_pool_bwd(torch::Tensor dy, torch::Tensor idx,
+                                          torch::Tensor p, torch::Tensor x,
+                                          int64_t R, int64_t S, int64_t pad,
+                                          int64_t convH, int64_t convW,
+                                          int64_t bkey, int64_t wkey);
 std::vector<torch::Tensor> head_xent_fwd(torch::Tensor h1, torch::Tensor w2,
                                          torch::Tensor b2,
                                          torch::Tensor labels,
@@ -290,6 +297,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("x"), py::arg("R"), py::arg("S"), py::arg("pad"),
           py::arg("H"), py::arg("W"), py::arg("gkey") = 0,
           "conv dgrad + wgrad in one launch: (dx, dw)");
+    m.def("conv1_pool_bwd_ok", &conv1_pool_bwd_ok, py::arg("dy"),
+          py::arg("x"), py::arg("R"), py::arg("S"), py::arg("pad"),
+          py::arg("convH"), py::arg("convW"),
+          "whether conv1_pool_bwd runs the single paired launch");
+    m.def("conv1_pool_bwd", &conv1_pool_bwd, py::arg("dy"), py::arg("idx"),
+          py::arg("p"), py::arg("x"), py::arg("R"), py::arg("S"),
+          py::arg("pad"), py::arg("convH"), py::arg("convW"),
+          py::arg("bkey") = 0, py::arg("wkey") = 0,
+          "conv->relu->pool backward without dgrad in one launch: (dw, db)");
     m.def("head_xent_fwd", &head_xent_fwd,
           "classifier tail forward: (logits, probs, loss), M<=64 H<=128 C<=16");
     m.def("head_xent_bwd", &head_xent_bwd,

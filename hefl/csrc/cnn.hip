@@ -32,8 +32,11 @@
 //                                  launch, role by block index, one LDS
 //                                  buffer sized to the larger role
 //                                  (conv_bwd_pair)
-//   conv_wgrad_small_kernel        Kout<=64 & RSC<=16 first-layer wgrad:
-//                                  waves split over pixels, LDS reduce
+//   conv_wgrad_small_body<GATED> / conv_wgrad_small_kernel
+//                                  Kout<=64 & RSC<=16 first-layer wgrad:
+//                                  waves split over pixels, LDS reduce;
+//                                  GATED stages its dy tile from the pooled
+//                                  gradient / argmax / pooled activation
 //   sum_slabs_f32_kernel           lane-parallel split-K slab reduction
 //   xcd_remap                      consecutive conv M-tiles -> one XCD's L2
 //   conv_fwd_glds64_kernel         BK=64 two-buffer fwd (measured slower at
@@ -48,9 +51,14 @@
 //                                  pool fwd + argmax byte (octet: 16-B
 //                                  loads + packed 8-B argmax store)
 //   maxpool2x2_bwd_gather_kernel   gather-form pool bwd (no scatter/fill)
-//   pool_relu_bias_bwd2_kernel     FUSED conv->relu->pool backward: one
+//   pool_relu_bias_bwd2_body<DYM> / pool_relu_bias_bwd2_kernel
+//                                  FUSED conv->relu->pool backward: one
 //                                  thread per 2x2 block x 8 channels,
 //                                  ReLU gate on the POOLED output
+//   conv1_pool_bwd_kernel          first-layer backward (no dgrad) in ONE
+//                                  launch, role by block index: the bias
+//                                  part of the kernel above (DYM=false) +
+//                                  the GATED small wgrad (conv1_pool_bwd)
 //   pool_relu_bias_bwd_scalar_kernel  K%8!=0 fallback (LeNet), lane-reduce
 //   dense_head2_bwd_kernel         single-launch 2-layer head backward
 //                                  (measured slower end-to-end; HEFL_HEAD2)
@@ -1890,14 +1898,30 @@ conv_bwd_pair_kernel(const unsigned short* __restrict__ dy,
 // 28x28x1 model's conv1): the generic 64xBN tile wastes 3/4 of its waves on
 // out-of-range rows. Here the 4 waves SPLIT over pixels (each owns 32 of a
 // 128-pixel iteration) and reduce their partial accumulators through LDS at
-// the end; grid.z chunks pixels further. ----
-__global__ void __launch_bounds__(TPB)
-conv_wgrad_small_kernel(const unsigned short* __restrict__ dy,
-                        const unsigned short* __restrict__ x,
-                        float* __restrict__ dw, ConvShape s, int k_chunks) {
-    __shared__ unsigned short Dys[128][64];
-    __shared__ unsigned short Xp[128][16];
-    __shared__ float red[4][16 * 16];
+// the end; grid.z chunks pixels further.
+//
+// The tile is a __device__ body over its LDS arrays and a virtual chunk
+// index bz, shared by conv_wgrad_small_kernel and conv1_pool_bwd_kernel.
+// GATED changes ONLY how Dys is staged: dy is then the POOLED gradient
+// [N,PH,PW,Kout] of a conv->relu->maxpool2x2 block and the un-pooled gated
+// gradient pool_relu_bias_bwd2_kernel would have written is rebuilt octet by
+// octet from dy / idx / p (the pooled cell of conv pixel (oh, ow) is
+// (oh>>1, ow>>1); a cell in the row or column a floor pool drops is zero).
+// Everything after the staging sees the same LDS bits either way. ----
+__device__ __forceinline__ bool pool_act(unsigned short pv) {
+    return (pv & 0x7fffu) != 0 && !(pv & 0x8000u);
+}
+
+template <bool GATED>
+__device__ __forceinline__ void
+conv_wgrad_small_body(unsigned short (&Dys)[128][64],
+                      unsigned short (&Xp)[128][16], float (&red)[4][16 * 16],
+                      const int bz, const unsigned short* __restrict__ dy,
+                      const uint8_t* __restrict__ idx,
+                      const unsigned short* __restrict__ p,
+                      const unsigned short* __restrict__ x,
+                      float* __restrict__ dw, const ConvShape& s,
+                      const int k_chunks, const int PH, const int PW) {
     const int tid = threadIdx.x;
     const int wave = tid >> 6;
     const int lane = tid & 63;
@@ -1906,7 +1930,7 @@ conv_wgrad_small_kernel(const unsigned short* __restrict__ dy,
     const int KK = s.N * s.OH * s.OW;
     const int FM = (M + 15) / 16;
     const int chunk = (KK + k_chunks - 1) / k_chunks;
-    const int kbeg = blockIdx.z * chunk;
+    const int kbeg = bz * chunk;
     const int kend = min(kbeg + chunk, KK);
     const bool fast_dy = (s.Kout % 8 == 0);
 
@@ -1917,7 +1941,39 @@ conv_wgrad_small_kernel(const unsigned short* __restrict__ dy,
     for (int p0 = kbeg; p0 < kend; p0 += 128) {
         // stage dy [128][Kout]
         for (int i = tid; i < 128 * (M / 8 > 0 ? M / 8 : 1); i += TPB) {
-            if (fast_dy) {
+            if (GATED) {
+                // host envelope: Kout % 8 == 0 and Kout / 8 a power of two
+                const int lg = 31 - __clz(M >> 3);
+                const int pix = i >> lg;
+                const int koc = (i - (pix << lg)) * 8;
+                const int kpix = p0 + pix;
+                u16x8 g = {};
+                if (kpix < kend) {
+                    const int n_ = (int)fdiv((unsigned)kpix, s.fOHOW);
+                    const int rem = kpix - n_ * (s.OH * s.OW);
+                    const int oh = (int)fdiv((unsigned)rem, s.fOW);
+                    const int ow = rem - oh * s.OW;
+                    const int ph = oh >> 1, pw = ow >> 1;
+                    if (ph < PH && pw < PW) {
+                        const int64_t o =
+                            (((int64_t)n_ * PH + ph) * PW + pw) * M + koc;
+                        const u16x8 d8 =
+                            *reinterpret_cast<const u16x8*>(&dy[o]);
+                        const u16x8 p8 = *reinterpret_cast<const u16x8*>(&p[o]);
+                        const uint64_t i8 =
+                            *reinterpret_cast<const uint64_t*>(idx + o);
+                        const int q = ((oh & 1) << 1) | (ow & 1);
+                        // predicated selects, no runtime-indexed array
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) {
+                            const int pos = (int)((i8 >> (8 * j)) & 3);
+                            g[j] = (pool_act(p8[j]) && pos == q)
+                                       ? d8[j] : (unsigned short)0;
+                        }
+                    }
+                }
+                *reinterpret_cast<u16x8*>(&Dys[pix][koc]) = g;
+            } else if (fast_dy) {
                 const int pix = i / (M / 8);
                 const int koc = (i % (M / 8)) * 8;
                 unsigned short* dst = &Dys[pix][koc];
@@ -2000,13 +2056,24 @@ conv_wgrad_small_kernel(const unsigned short* __restrict__ dy,
                     // stored exactly once -> no atomics, no zero-fill; a
                     // tiny epilogue sums the slices)
                     float* dst = dw + (k_chunks > 1
-                                           ? (int64_t)blockIdx.z * M * NN : 0);
+                                           ? (int64_t)bz * M * NN : 0);
                     dst[(int64_t)ko * NN + sub] = v;
                 }
             }
         }
         __syncthreads();
     }
+}
+
+__global__ void __launch_bounds__(TPB)
+conv_wgrad_small_kernel(const unsigned short* __restrict__ dy,
+                        const unsigned short* __restrict__ x,
+                        float* __restrict__ dw, ConvShape s, int k_chunks) {
+    __shared__ unsigned short Dys[128][64];
+    __shared__ unsigned short Xp[128][16];
+    __shared__ float red[4][16 * 16];
+    conv_wgrad_small_body<false>(Dys, Xp, red, blockIdx.z, dy, nullptr,
+                                 nullptr, x, dw, s, k_chunks, 0, 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -2377,19 +2444,27 @@ __global__ void maxpool_fwd_oct_kernel(const unsigned short* __restrict__ x,
 // before pool, so p > 0 iff the argmax cell was active) — the full pre-pool
 // activation y is neither read nor saved for backward anymore. dy/idx/p are
 // read ONCE per output cell (the row-per-thread form re-read them 4x).
-__global__ void pool_relu_bias_bwd2_kernel(
+//
+// A __device__ body over its LDS partials dbs[K] and a virtual block index /
+// block count (bid, nblk), shared by pool_relu_bias_bwd2_kernel and
+// conv1_pool_bwd_kernel's bias role. DYM = false drops the dym stores and
+// nothing else: the thread-to-(2x2 block, octet) mapping, the per-thread
+// acc order and the skip-zero LDS and global atomics into db are the same
+// statements, so db is the same sum of the same partials.
+template <bool DYM>
+__device__ __forceinline__ void pool_relu_bias_bwd2_body(
+    float* dbs, const int bid, const int nblk,
     const unsigned short* __restrict__ dy, const uint8_t* __restrict__ idx,
     const unsigned short* __restrict__ p, unsigned short* __restrict__ dym,
     float* __restrict__ db, int64_t total8, int K, int H, int W, int OH,
     int OW, int HB, int WB, FastDiv fOct, FastDiv fWB, FastDiv fHB) {
-    extern __shared__ float dbs[];  // [K]
     const int noct = K >> 3;
     for (int c = threadIdx.x; c < K; c += blockDim.x) dbs[c] = 0.f;
     __syncthreads();
     float acc[8] = {0.f};
     int my_oct = -1;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-         i < total8; i += (int64_t)gridDim.x * blockDim.x) {
+    for (int64_t i = bid * (int64_t)blockDim.x + threadIdx.x;
+         i < total8; i += (int64_t)nblk * blockDim.x) {
         unsigned t = fdiv((unsigned)i, fOct);
         const int oct = (int)((unsigned)i - t * noct);
         my_oct = oct;  // constant per thread: stride % noct == 0 (noct pow2)
@@ -2410,7 +2485,7 @@ __global__ void pool_relu_bias_bwd2_kernel(
             const uint64_t i8 = *reinterpret_cast<const uint64_t*>(idx + o);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const bool act = (p8[j] & 0x7fffu) != 0 && !(p8[j] & 0x8000u);
+                const bool act = pool_act(p8[j]);
                 const int pos = (int)((i8 >> (8 * j)) & 3);
                 const unsigned short dv = act ? d8[j] : (unsigned short)0;
                 if (act) acc[j] += bf2f(d8[j]);
@@ -2420,14 +2495,17 @@ __global__ void pool_relu_bias_bwd2_kernel(
                 g3[j] = pos == 3 ? dv : (unsigned short)0;
             }
         }
-        const int64_t r0 = (((int64_t)n * H + ih) * W + iw) * K + oct * 8;
-        *reinterpret_cast<u16x8*>(&dym[r0]) = g0;
-        if (iw + 1 < W)
-            *reinterpret_cast<u16x8*>(&dym[r0 + K]) = g1;
-        if (ih + 1 < H) {
-            *reinterpret_cast<u16x8*>(&dym[r0 + (int64_t)W * K]) = g2;
+        if (DYM) {
+            const int64_t r0 = (((int64_t)n * H + ih) * W + iw) * K + oct * 8;
+            *reinterpret_cast<u16x8*>(&dym[r0]) = g0;
             if (iw + 1 < W)
-                *reinterpret_cast<u16x8*>(&dym[r0 + (int64_t)W * K + K]) = g3;
+                *reinterpret_cast<u16x8*>(&dym[r0 + K]) = g1;
+            if (ih + 1 < H) {
+                *reinterpret_cast<u16x8*>(&dym[r0 + (int64_t)W * K]) = g2;
+                if (iw + 1 < W)
+                    *reinterpret_cast<u16x8*>(&dym[r0 + (int64_t)W * K + K]) =
+                        g3;
+            }
         }
     }
     if (my_oct >= 0) {
@@ -2436,12 +2514,54 @@ __global__ void pool_relu_bias_bwd2_kernel(
             if (acc[j] != 0.f) atomicAdd(dbs + my_oct * 8 + j, acc[j]);
     }
     __syncthreads();
-    if (gridDim.x == 1) {  // small layers: direct store, db needs no zero-fill
+    if (nblk == 1) {  // small layers: direct store, db needs no zero-fill
         for (int c = threadIdx.x; c < K; c += blockDim.x) db[c] = dbs[c];
     } else {
         for (int c = threadIdx.x; c < K; c += blockDim.x)
             if (dbs[c] != 0.f) atomicAdd(db + c, dbs[c]);
     }
+}
+
+__global__ void pool_relu_bias_bwd2_kernel(
+    const unsigned short* __restrict__ dy, const uint8_t* __restrict__ idx,
+    const unsigned short* __restrict__ p, unsigned short* __restrict__ dym,
+    float* __restrict__ db, int64_t total8, int K, int H, int W, int OH,
+    int OW, int HB, int WB, FastDiv fOct, FastDiv fWB, FastDiv fHB) {
+    extern __shared__ float dbs[];  // [K]
+    pool_relu_bias_bwd2_body<true>(dbs, blockIdx.x, gridDim.x, dy, idx, p,
+                                   dym, db, total8, K, H, W, OH, OW, HB, WB,
+                                   fOct, fWB, fHB);
+}
+
+// Conv1's whole backward up to the slab sum in ONE launch (conv1 has no
+// dgrad, so the un-pooled gated gradient has the small wgrad as its only
+// consumer and is never written). Role by linear block index, as in
+// conv_bwd_pair_kernel: blocks [0, n_db) run pool_relu_bias_bwd2's bias part
+// (db by the same per-thread partials and the same fp32 atomics), the other
+// kc blocks the small wgrad tile with its dy tile gated on the fly from the
+// pooled dy / idx / p. The bias role's K <= 64 LDS partials live in the
+// wgrad role's red[] array, so the LDS is the wgrad kernel's own 24 KB. The
+// host pairs only where n_db + kc blocks fit one per CU.
+__global__ void __launch_bounds__(TPB)
+conv1_pool_bwd_kernel(const unsigned short* __restrict__ dy,
+                      const uint8_t* __restrict__ idx,
+                      const unsigned short* __restrict__ p,
+                      const unsigned short* __restrict__ x,
+                      float* __restrict__ dw, float* __restrict__ db,
+                      ConvShape s, int n_db, int kc, int64_t total8, int PH,
+                      int PW, int HB, int WB, FastDiv fOct, FastDiv fWB,
+                      FastDiv fHB) {
+    __shared__ unsigned short Dys[128][64];
+    __shared__ unsigned short Xp[128][16];
+    __shared__ float red[4][16 * 16];
+    const int bid = blockIdx.x;
+    if (bid < n_db)
+        pool_relu_bias_bwd2_body<false>(&red[0][0], bid, n_db, dy, idx, p,
+                                        nullptr, db, total8, s.Kout, s.OH,
+                                        s.OW, PH, PW, HB, WB, fOct, fWB, fHB);
+    else
+        conv_wgrad_small_body<true>(Dys, Xp, red, bid - n_db, dy, idx, p, x,
+                                    dw, s, kc, PH, PW);
 }
 
 // Scalar fallback for K % 8 != 0 trunk layers// Scalar fallback for K % 8 != 0 trunk layers (LeNet-5's 6/16 filters):
@@ -4664,6 +4784,19 @@ static bool wgrad_k32_bkp128() {
     return bkp128;
 }
 
+// conv2d_wgrad's small-shape dispatch and chunk count, shared with
+// conv1_pool_bwd's envelope.
+static bool wgrad_takes_small(const ConvShape& s) {
+    return s.R * s.S * s.C <= 16 && s.Kout <= 64;
+}
+
+// measured: KK/64 slabs (338 blocks) LOST to KK/256 (84) — the slab reduce
+// outgrows the parallel gain; this path is latency- not occupancy-bound
+static int wgrad_small_chunks(const ConvShape& s) {
+    const int KK = s.N * s.OH * s.OW;
+    return std::max(1, std::min(ceildiv(KK, 256), 512));
+}
+
 static int wgrad_k32_chunks(const ConvShape& s) {
     const int NN = s.R * s.S * s.C;
     const int KK = s.N * s.OH * s.OW;
@@ -4692,7 +4825,7 @@ torch::Tensor conv2d_wgrad(torch::Tensor dy, torch::Tensor x, int64_t stride,
     const int NN = s.R * s.S * s.C;
     const int KK = s.N * s.OH * s.OW;
     const bool big = NN > 16;
-    const bool small_fast = (!big) && s.Kout <= 64;
+    const bool small_fast = wgrad_takes_small(s);
     const bool glds_ok = big && (s.C % 8 == 0) && (s.Kout % 8 == 0);
     const int bn = big ? 64 : 16;
     // split-K to fill the chip: target >= 512 blocks (2 per CU)
@@ -4703,10 +4836,7 @@ torch::Tensor conv2d_wgrad(torch::Tensor dy, torch::Tensor x, int64_t stride,
     if (small_fast) {
         auto dw = torch::empty({s.Kout, R, S, s.C},
                                x.options().dtype(torch::kFloat32));
-        // measured: KK/64 slabs (338 blocks) LOST to KK/256 (84) — the
-        // slab reduce outgrows the parallel gain; this path is latency-
-        // not occupancy-bound
-        int kc = std::max(1, std::min(ceildiv(KK, 256), 512));
+        const int kc = wgrad_small_chunks(s);
         if (kc == 1) {
             hipLaunchKernelGGL(conv_wgrad_small_kernel, dim3(1, 1, 1),
                                dim3(TPB), 0, stream, bf_ptr(dy), bf_ptr(x),
@@ -5248,6 +5378,20 @@ std::vector<torch::Tensor> relu_bias_bwd(torch::Tensor dy, torch::Tensor y,
     return {dym, db};
 }
 
+// pool_relu_bias_bwd's octet-kernel dispatch and grid, shared with
+// conv1_pool_bwd's envelope.
+static bool pool_bwd_takes_octet(int K) {
+    const int noct = K >> 3;
+    return (K & 7) == 0 && (noct & (noct - 1)) == 0 && noct <= 256;
+}
+
+// measured: forcing ONE block on small layers to skip the db zero-fill
+// serialized the whole layer onto one CU (-30% on the headline config) —
+// keep the parallel grid and pay the 4.7 us fill
+static int pool_bwd_octet_blocks(int64_t total8) {
+    return (int)std::min<int64_t>(ceildiv(total8, 256), 4096);
+}
+
 std::vector<torch::Tensor> pool_relu_bias_bwd(torch::Tensor dy,
                                               torch::Tensor idx,
                                               torch::Tensor p, int64_t H,
@@ -5259,14 +5403,11 @@ std::vector<torch::Tensor> pool_relu_bias_bwd(torch::Tensor dy,
     auto dym = torch::empty({N, H, W, (int64_t)K}, dyc.options());
     auto stream = at::cuda::getCurrentCUDAStream();
     const int noct = K >> 3;
-    if ((K & 7) == 0 && (noct & (noct - 1)) == 0 && noct <= 256) {
+    if (pool_bwd_takes_octet(K)) {
         // 2x2-block octet kernel: dy/idx/p read once per output cell
         const int HB = (int)((H + 1) / 2), WB = (int)((W + 1) / 2);
         const int64_t total8 = (int64_t)N * HB * WB * noct;
-        // measured: forcing ONE block on small layers to skip the db
-        // zero-fill serialized the whole layer onto one CU (-30% on the
-        // headline config) — keep the parallel grid and pay the 4.7 us fill
-        int blocks = (int)std::min<int64_t>(ceildiv(total8, 256), 4096);
+        const int blocks = pool_bwd_octet_blocks(total8);
         torch::Tensor db;
         bool db_pooled = false;
         if (blocks > 1 && gkey)
@@ -5307,6 +5448,103 @@ std::vector<torch::Tensor> pool_relu_bias_bwd(torch::Tensor dy,
                        db.data_ptr<float>(), M, K, rpb, (int)H, (int)W, OH,
                        OW, fdiv_make((unsigned)W), fdiv_make((unsigned)H));
     return {dym, db};
+}
+
+// Pairing envelope for conv1_pool_bwd: pool_relu_bias_bwd would run the
+// octet kernel, conv2d_wgrad the small tile, and both roles' blocks together
+// fit one per CU (stride is 1 by construction: the conv->relu->pool block).
+static bool conv1_pool_bwd_plan(const ConvShape& s, int& n_db, int& kc,
+                                int64_t& total8) {
+    if (!pool_bwd_takes_octet(s.Kout) || !wgrad_takes_small(s)) return false;
+    const int HB = (s.OH + 1) / 2, WB = (s.OW + 1) / 2;
+    total8 = (int64_t)s.N * HB * WB * (s.Kout >> 3);
+    n_db = pool_bwd_octet_blocks(total8);
+    kc = wgrad_small_chunks(s);
+    const int cus = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+    return n_db + kc <= cus;
+}
+
+static ConvShape conv1_pool_bwd_shape(const torch::Tensor& dy,
+                                      const torch::Tensor& x, int64_t R,
+                                      int64_t S, int64_t pad, int64_t convH,
+                                      int64_t convW) {
+    TORCH_CHECK(dy.dim() == 4 && x.dim() == 4 && x.size(0) == dy.size(0) &&
+                convH == x.size(1) + 2 * pad - R + 1 &&
+                convW == x.size(2) + 2 * pad - S + 1 &&
+                dy.size(1) == convH / 2 && dy.size(2) == convW / 2,
+                "conv1_pool_bwd shapes");
+    ConvShape s;
+    s.N = (int)x.size(0); s.H = (int)x.size(1); s.W = (int)x.size(2);
+    s.C = (int)x.size(3);
+    s.Kout = (int)dy.size(3); s.R = (int)R; s.S = (int)S;
+    s.stride = 1; s.pad = (int)pad;
+    s.OH = (int)convH; s.OW = (int)convW;
+    fill_magic(s);
+    return s;
+}
+
+bool conv1_pool_bwd_ok(torch::Tensor dy, torch::Tensor x, int64_t R,
+                       int64_t S, int64_t pad, int64_t convH, int64_t convW) {
+    if (!dy.is_cuda()) return false;
+    int n_db, kc;
+    int64_t total8;
+    return conv1_pool_bwd_plan(
+        conv1_pool_bwd_shape(dy, x, R, S, pad, convH, convW), n_db, kc,
+        total8);
+}
+
+// Backward of a conv->relu->maxpool2x2 block that needs NO input gradient
+// (the first layer): (dw, db) from the pooled gradient. ONE
+// conv1_pool_bwd_kernel launch (+ the slab sum) inside the envelope above,
+// pool_relu_bias_bwd + conv2d_wgrad outside it. Same dw bits either way; db
+// is the same partials summed by the same fp32 atomics.
+std::vector<torch::Tensor> conv1_pool_bwd(torch::Tensor dy, torch::Tensor idx,
+                                          torch::Tensor p, torch::Tensor x,
+                                          int64_t R, int64_t S, int64_t pad,
+                                          int64_t convH, int64_t convW,
+                                          int64_t bkey, int64_t wkey) {
+    CHECK_GPU(dy);
+    TORCH_CHECK(dy.is_contiguous() && idx.is_contiguous() &&
+                p.is_contiguous() && x.is_contiguous());
+    TORCH_CHECK(p.sizes() == dy.sizes() && idx.sizes() == dy.sizes());
+    const ConvShape s = conv1_pool_bwd_shape(dy, x, R, S, pad, convH, convW);
+    int n_db = 0, kc = 0;
+    int64_t total8 = 0;
+    if (!conv1_pool_bwd_plan(s, n_db, kc, total8)) {
+        auto r = pool_relu_bias_bwd(dy, idx, p, convH, convW, bkey);
+        auto dw = conv2d_wgrad(r[0], x, 1, R, S, pad, wkey);
+        return {dw, r[1]};
+    }
+    auto stream = at::cuda::getCurrentCUDAStream();
+    auto f32 = x.options().dtype(torch::kFloat32);
+    const int PH = (int)dy.size(1), PW = (int)dy.size(2);
+    const int HB = (s.OH + 1) / 2, WB = (s.OW + 1) / 2;
+    const int noct = s.Kout >> 3;
+    // db allocation / grad_buf routing / fill-skip: pool_relu_bias_bwd
+    torch::Tensor db;
+    bool db_pooled = false;
+    if (n_db > 1 && bkey)
+        db = grad_buf(bkey, {s.Kout}, dy.options(), stream, db_pooled);
+    if (!db_pooled)
+        db = n_db == 1 ? torch::empty({s.Kout}, f32)
+                       : torch::zeros({s.Kout}, f32);
+    // dw: conv2d_wgrad's small branch (per-chunk slabs, no atomics)
+    auto dw = torch::empty({s.Kout, R, S, s.C}, f32);
+    const int64_t total = (int64_t)s.Kout * R * S * s.C;
+    torch::Tensor slab;
+    if (kc > 1) slab = torch::empty({kc, total}, f32);
+    hipLaunchKernelGGL(conv1_pool_bwd_kernel, dim3(n_db + kc), dim3(TPB), 0,
+                       stream, bf_ptr(dy), idx.data_ptr<uint8_t>(), bf_ptr(p),
+                       bf_ptr(x), (kc > 1 ? slab : dw).data_ptr<float>(),
+                       db.data_ptr<float>(), s, n_db, kc, total8, PH, PW, HB,
+                       WB, fdiv_make((unsigned)noct), fdiv_make((unsigned)WB),
+                       fdiv_make((unsigned)HB));
+    if (kc > 1)
+        hipLaunchKernelGGL(sum_slabs_f32_kernel,
+                           dim3((int)((total + 15) / 16)), dim3(256), 0,
+                           stream, slab.data_ptr<float>(),
+                           dw.data_ptr<float>(), total, kc);
+    return {dw, db};
 }
 
 std::vector<torch::Tensor> dense_head2_bwd(torch::Tensor dlogits,

@@ -92,6 +92,13 @@ _CONV_POOL = os.getenv("HEFL_CONV_POOL", "1") != "0"
 # index, where both fit one block per CU (conv_bwd_pair_ok); same tile
 # bodies, same outputs (tests/test_gpu_conv_bwd_pair.py).
 _CONV_BWD_PAIR = os.getenv("HEFL_CONV_BWD_PAIR", "1") != "0"
+# First-layer backward in one launch (default ON, HEFL_CONV1_BWD=0 restores
+# pool_relu_bias_bwd + conv2d_wgrad): a conv->relu->pool block that needs no
+# input gradient takes dw and db from ONE conv1_pool_bwd launch; the small
+# wgrad gates its tile on the fly from the pooled gradient, so the un-pooled
+# gated gradient is never written. Same dw bits, db by the same fp32 atomics
+# (tests/test_gpu_conv1_bwd_fused.py).
+_CONV1_BWD = os.getenv("HEFL_CONV1_BWD", "1") != "0"
 
 # Epoch-graph capture contract (fl/client.py sets this around warmup +
 # capture; HEFL_GRAPH_NO_ZERO=0 disables): while True, conv dw / bias db
@@ -267,7 +274,11 @@ class _ConvReluPoolFn(torch.autograd.Function):
     two full passes over the activation-gradient tensor); then dgrad and
     wgrad, as ONE conv_bwd_pair launch where the layer is small enough for
     both to fit one block per CU (conv_bwd_pair_ok; HEFL_CONV_BWD_PAIR=0 or
-    a larger layer: two launches, same outputs)."""
+    a larger layer: two launches, same outputs). A block that needs no input
+    gradient (the first layer) instead takes dw and db from ONE
+    conv1_pool_bwd launch, which never writes the gated gradient
+    (HEFL_CONV1_BWD=0, a channel-padded stem or a layer outside its
+    envelope: pool_relu_bias_bwd + conv2d_wgrad, same dw bits)."""
 
     @staticmethod
     def forward(ctx, x, w, b, pad: int):
@@ -301,9 +312,16 @@ class _ConvReluPoolFn(torch.autograd.Function):
         ch, cw = ctx.conv_hw
         Kout, R, S, C = w.shape
         bkey = ctx.bkey if GRAPH_NO_ZERO else 0
+        wg = ctx.wkey if (GRAPH_NO_ZERO and not ctx.cpad) else 0
+        if _CONV1_BWD and not ctx.needs_input_grad[0] and not ctx.cpad:
+            # one launch inside conv1_pool_bwd's envelope; outside it the
+            # wrapper runs pool_relu_bias_bwd + conv2d_wgrad as below
+            dw, db = _C().conv1_pool_bwd(dy.contiguous(), idx, p,
+                                         x.contiguous(), R, S, ctx.pad, ch,
+                                         cw, bkey=bkey, wkey=wg)
+            return None, dw, db, None
         dym, db = _C().pool_relu_bias_bwd(dy.contiguous(), idx, p, ch, cw,
                                           gkey=bkey)
-        wg = ctx.wkey if (GRAPH_NO_ZERO and not ctx.cpad) else 0
         fork = (_BWD_FORK and ctx.needs_input_grad[0]
                 and torch.cuda.is_current_stream_capturing())
         if (_CONV_BWD_PAIR and ctx.needs_input_grad[0] and not ctx.cpad
