@@ -235,12 +235,19 @@ class GpuBackend:
             pinv = [pow(P % q, -1, q) for q in self.primes[:l]]
             pinv_sh = [np.int64(np.uint64((v << 64) // q))
                        for v, q in zip(pinv, self.primes[:l])]
+
+            def rows(t):
+                # the top level takes every row: the full tables serve, and
+                # a process that only relinearizes there (the config #3
+                # aggregation) never launches a torch gather
+                return t if l == sp else t.index_select(0, idx)
+
             cache[l] = LevelTables(
                 idx=idx,
-                w=self.w.index_select(0, idx),
-                w_shoup=self.w_shoup.index_select(0, idx),
-                qs=self.qs.index_select(0, idx),
-                ratio_words=self.ratio_words.index_select(0, idx),
+                w=rows(self.w),
+                w_shoup=rows(self.w_shoup),
+                qs=rows(self.qs),
+                ratio_words=rows(self.ratio_words),
                 pinv=torch.tensor(pinv, dtype=torch.int64, device=self.device),
                 pinv_shoup=torch.tensor(np.array(pinv_sh, dtype=np.int64),
                                         device=self.device))
@@ -1027,24 +1034,23 @@ class CKKSContext:
         s = torch.where(s > q0 // 2, s - q0, s)  # ternary {-1,0,1}
         return self._to_rns_ntt(s, self.L + 1)
 
-    def relin_keygen(self, sk: torch.Tensor) -> torch.Tensor:
-        """Hybrid key-switching keys (digits = RNS limbs, one special prime P).
+    def _switching_key(self, sk_ext: torch.Tensor,
+                       target: torch.Tensor) -> torch.Tensor:
+        """Hybrid key-switching key (digits = RNS limbs, one special prime P)
+        from `target` [L+1, n] (NTT form) to the secret sk_ext [L+1, n].
 
-        rlk[d] = (-(a_d*s + e_d) + P*q̃_d*s², a_d) over the L+1 limbs
-        {q_0..q_{L-1}, P}. In RNS, P*q̃_d*s² is (P mod q_d)*s² at limb d and
-        0 elsewhere (q̃_d ≡ δ_{d,i} mod q_i, P ≡ 0 mod P). Key-switch noise
-        shrinks by 1/P at the final mod-down, which is what makes per-limb
-        digits sound (classic per-limb BV without P has q_max-sized noise).
-        Returns int64 [L, 2, L+1, n] in NTT form.
-        """
+        key[d] = (-(a_d*s + e_d) + P*q̃_d*target, a_d) over the L+1 limbs
+        {q_0..q_{L-1}, P}. In RNS, P*q̃_d*target is (P mod q_d)*target at limb
+        d and 0 elsewhere (q̃_d ≡ δ_{d,i} mod q_i, P ≡ 0 mod P). Key-switch
+        noise shrinks by 1/P at the final mod-down, which is what makes
+        per-limb digits sound (classic per-limb BV without P has q_max-sized
+        noise). Per digit the seeded host stream gives a_d first, e_d second:
+        every rank and the CPU and GPU contexts derive identical keys.
+        Returns int64 [L, 2, L+1, n] in NTT form."""
         L, n = self.L, self.n
         Lp = L + 1
         P = self.special
-        sk_ext = self._sk_extended(sk)            # [L+1, n]
-        s2 = torch.empty_like(sk_ext)
-        for i in range(Lp):
-            s2[i] = self.backend.modmul(sk_ext[i], sk_ext[i], i)
-        rlk = torch.empty((L, 2, Lp, n), dtype=torch.int64, device=self.device)
+        key = torch.empty((L, 2, Lp, n), dtype=torch.int64, device=self.device)
         for d in range(L):
             a = self._sample_uniform((Lp, n)).to(self.device)
             e = self._to_rns_ntt(self._sample_err((n,), host=True), Lp)
@@ -1054,78 +1060,31 @@ class CKKSContext:
                                       + e[i]), q)
                 if i == d:
                     b = torch.remainder(
-                        b + self.backend.modmul_scalar(s2[i], P % q, i), q)
-                rlk[d, 0, i] = b
-                rlk[d, 1, i] = a[i]
-        return rlk
+                        b + self.backend.modmul_scalar(target[i], P % q, i), q)
+                key[d, 0, i] = b
+                key[d, 1, i] = a[i]
+        return key
 
-    def _keyswitch(self, d2: torch.Tensor, rlk: torch.Tensor):
-        """Key-switch NTT-form d2 [..., L, n] through rlk; returns the pair
-        (ks0, ks1) each [..., L, n] to add to (c0, c1).
-
-        GPU path is fully fused: one INTT set over all
-        digits, one lift launch, one NTT set, ONE inner-product kernel over
-        all digits x limbs, then a fused mod-down — ~12 launches total
-        instead of the O(L*(L+1)) per-digit/per-limb Python loop."""
-        L = d2.shape[-2]
-        Lp = L + 1
-        n = self.n
-        if self.device.type == "cuda":
-            be = self.backend
-            c = be.ntt_all(d2, inverse=True)           # digits -> coeff domain
-            dig = be.bcast_center_mod(c, 0, Lp)        # [..., L, Lp, n]
-            dig = be.ntt_all(dig)                      # NTT over the Lp limbs
-            acc0, acc1 = be._C.ks_inner(dig.contiguous(), rlk.contiguous(),
-                                        be.qs, be.ratio_words, L, Lp, n)
-            P = self.special
-            inv = [pow(P % self._q(i), -1, self._q(i)) for i in range(L)]
-            outs = []
-            for acc in (acc0, acc1):
-                cl = be.ntt(acc[..., L, :], L, inverse=True)
-                r_ntt = be.ntt_all(be.bcast_center_mod(cl, P, L))
-                diff = be.modsub_limbs(acc, r_ntt, L)
-                outs.append(be.modmul_scalar_limbs(diff, inv))
-            return outs[0], outs[1]
-        lead = d2.shape[:-2]
-        acc0 = torch.zeros(lead + (Lp, n), dtype=torch.int64, device=d2.device)
-        acc1 = torch.zeros_like(acc0)
-        for d in range(L):
-            # digit d: coefficient-domain residues mod q_d, lifted to every limb
-            c = self.backend.ntt(d2[..., d, :], d, inverse=True)
-            for i in range(Lp):
-                q = self._q(i)
-                dig = self.backend.ntt(torch.remainder(c, q), i)
-                acc0[..., i, :] = torch.remainder(
-                    acc0[..., i, :] + self.backend.modmul(
-                        dig, rlk[d, 0, i].expand_as(dig).contiguous(), i), q)
-                acc1[..., i, :] = torch.remainder(
-                    acc1[..., i, :] + self.backend.modmul(
-                        dig, rlk[d, 1, i].expand_as(dig).contiguous(), i), q)
-        # mod-down by the special prime P (exact division with rounding,
-        # same structure as rescale_data but dropping the special limb)
-        P = self.special
-        P_half = P // 2
-        outs = []
-        for acc in (acc0, acc1):
-            cl = self.backend.ntt(acc[..., L, :], L, inverse=True)
-            cl_c = torch.where(cl > P_half, cl - P, cl)
-            out = acc[..., :L, :].clone()
-            for i in range(L):
-                q = self._q(i)
-                r_ntt = self.backend.ntt(torch.remainder(cl_c, q), i)
-                diff = torch.remainder(out[..., i, :] - r_ntt, q)
-                out[..., i, :] = self.backend.modmul_scalar(
-                    diff, pow(P % q, -1, q), i)
-            outs.append(out)
-        return outs[0], outs[1]
+    def relin_keygen(self, sk: torch.Tensor) -> torch.Tensor:
+        """Relinearization key: the switching key from s² to s
+        (_switching_key), int64 [L, 2, L+1, n] in NTT form."""
+        sk_ext = self._sk_extended(sk)            # [L+1, n]
+        s2 = torch.empty_like(sk_ext)
+        for i in range(self.L + 1):
+            s2[i] = self.backend.modmul(sk_ext[i], sk_ext[i], i)
+        return self._switching_key(sk_ext, s2)
 
     def mul_ct(self, a: Ciphertext, b: Ciphertext, rlk: torch.Tensor) -> Ciphertext:
-        """ct x ct multiply + relinearize (no rescale; call rescale after)."""
+        """ct x ct multiply + relinearize at any level 1..L (no rescale; call
+        rescale after)."""
         if rlk is None:
             raise ValueError(
                 "ct x ct multiply needs relinearization keys — run "
                 "relin_keygen(sk) (Pyfhel API: relinKeyGen) first")
-        assert a.level == b.level
+        if a.level != b.level:
+            raise ValueError(
+                f"ct x ct multiply needs both operands at the same level, "
+                f"got {a.level} and {b.level}")
         L = a.level
         if self.device.type == "cuda":
             # one fused tensor-product launch (d0, d1, d2 together)
@@ -1145,7 +1104,7 @@ class CKKSContext:
                          + self.backend.modmul(a1[..., i, :], b0[..., i, :], i))
                 d1[..., i, :] = torch.remainder(cross, q)
                 d2[..., i, :] = self.backend.modmul(a1[..., i, :], b1[..., i, :], i)
-        ks0, ks1 = self._keyswitch(d2, rlk)
+        ks0, ks1 = self._keyswitch(d2, rlk, L)
         limbs = list(range(L))
         c0 = self._modadd(d0, ks0, limbs)
         c1 = self._modadd(d1, ks1, limbs)
@@ -1215,11 +1174,8 @@ class CKKSContext:
         """Galois keys {element g: int64 [L, 2, L+1, n]}, one per rotation
         step (default: +-2^k) plus conjugation on request.
 
-        Same shape and distribution as relin_keygen's output; digit d hides
-        P*q~_d*sigma_g(s) instead of P*q~_d*s^2 — in RNS (P mod q_d) *
-        sigma_g(s) at limb d and nothing elsewhere. Sampled on the host from
-        the context's seeded stream like every key, so all ranks and the CPU
-        and GPU contexts derive identical keys."""
+        Each is the switching key from sigma_g(s) to s (_switching_key),
+        drawn in the order the elements are given."""
         if sk is None:
             raise ValueError(
                 "galois_keygen needs the secret key; under key_mode="
@@ -1228,9 +1184,6 @@ class CKKSContext:
         elements = [self.galois_element(s) for s in steps]
         if conjugate:
             elements.append(self.galois_element(conjugate=True))
-        L, n = self.L, self.n
-        Lp = L + 1
-        P = self.special
         sk_ext = self._sk_extended(sk)            # [L+1, n]
         keys: Dict[int, torch.Tensor] = {}
         for g in elements:
@@ -1238,21 +1191,7 @@ class CKKSContext:
                 continue
             perm = self._galois_tables(g).perm
             s_g = sk_ext.index_select(-1, perm)   # sigma_g(s), NTT form
-            gk = torch.empty((L, 2, Lp, n), dtype=torch.int64,
-                             device=self.device)
-            for d in range(L):
-                a = self._sample_uniform((Lp, n)).to(self.device)
-                e = self._to_rns_ntt(self._sample_err((n,), host=True), Lp)
-                for i in range(Lp):
-                    q = self._q(i)
-                    b = torch.remainder(-(self.backend.modmul(a[i], sk_ext[i], i)
-                                          + e[i]), q)
-                    if i == d:
-                        b = torch.remainder(
-                            b + self.backend.modmul_scalar(s_g[i], P % q, i), q)
-                    gk[d, 0, i] = b
-                    gk[d, 1, i] = a[i]
-            keys[g] = gk
+            keys[g] = self._switching_key(sk_ext, s_g)
         return keys
 
     def _key_at_level(self, key: torch.Tensor, l: int) -> torch.Tensor:
@@ -1286,63 +1225,81 @@ class CKKSContext:
         composed of torch gather / where / stack (PERFORMANCE.md: slower)."""
         return os.getenv("HEFL_GALOIS_FUSED", "1") != "0"
 
-    def _keyswitch_level(self, x: torch.Tensor, key: torch.Tensor, l: int,
-                         g: Optional[int] = None):
-        """Level-aware hybrid key-switch of NTT-form x [..., l, n] (l <= L
-        chain limbs) through `key` [L, 2, L+1, n]; returns (ks0, ks1), each
-        [..., l, n]. Uses digits 0..l-1 of the key over the limbs
-        {q_0..q_{l-1}, P}. With g given, switches sigma_g(x) instead — the
-        automorphism is applied to the coefficient-domain digits on the way.
+    @staticmethod
+    def _dot_mod(a: torch.Tensor, b: torch.Tensor, q: int, dim: int) -> torch.Tensor:
+        """Exact sum over `dim` of a * b mod q (broadcasting, python ints):
+        the CPU oracle's inner product."""
+        r = (a.cpu().numpy().astype(object)
+             * b.cpu().numpy().astype(object)).sum(axis=dim) % q
+        return torch.from_numpy(r.astype(np.int64))
 
-        GPU: the launch sequence of _keyswitch on tables gathered at rows
-        [0..l-1, L] (GpuBackend.level_tables)."""
+    def _hoist_digits(self, x: torch.Tensor, l: int,
+                   gt: Optional[GaloisTables] = None) -> torch.Tensor:
+        """NTT-form key-switch digits of x [..., l, n]:
+        D[.., d, j, :] = NTT(c_d mod q_j) over the limbs {q_0..q_{l-1}, P},
+        c_d = INTT(x[.., d, :]) in [0, q_d) — or, with gt given, sigma_g of
+        it, applied in the coefficient domain before the lift. Returns
+        [..., l, l+1, n].
+
+        GPU: intt_limbs, one lift launch on the tables gathered at rows
+        [0..l-1, L] (GpuBackend.level_tables), in-place ntt_limbs."""
         if x.shape[-2] != l or not 1 <= l <= self.L:
             raise ValueError(f"expected [.., {l}, n] with 1 <= l <= {self.L}, "
                              f"got {tuple(x.shape)}")
-        if tuple(key.shape) != (self.L, 2, self.L + 1, self.n):
-            raise ValueError(
-                f"switching key must be [{self.L}, 2, {self.L + 1}, {self.n}], "
-                f"got {tuple(key.shape)}")
-        n = self.n
-        gt = None if g is None else self._galois_tables(g)
-        idx = list(range(l)) + [self.L]
         if self.device.type == "cuda":
             be = self.backend
             tb = be.level_tables(l)
-            kl = self._key_at_level(key, l)
             c = be.ntt_all(x, inverse=True)            # digits -> coeff domain
-            if gt is None:
-                dig = be._C.bcast_center_mod(c, 0, tb.qs, tb.ratio_words, l + 1)
-            elif self._galois_fused():
+            if gt is not None and self._galois_fused():
                 dig = be.galois_lift(c, gt.ginv, tb)
             else:
-                c = self._coeff_automorphism(c, be.qs[:l].view(l, 1), gt)
+                if gt is not None:
+                    c = self._coeff_automorphism(c, be.qs[:l].view(l, 1), gt)
                 dig = be._C.bcast_center_mod(c.contiguous(), 0, tb.qs,
                                              tb.ratio_words, l + 1)
-            be.ntt_level_(dig, tb)                     # [..., l, l+1, n]
-            acc0, acc1 = be._C.ks_inner(dig, kl, tb.qs, tb.ratio_words,
-                                        l, l + 1, n)
-            return self._moddown_level(acc0, acc1, l)
-        lead = x.shape[:-2]
-        acc0 = torch.zeros(lead + (l + 1, n), dtype=torch.int64, device=x.device)
-        acc1 = torch.zeros_like(acc0)
+            return be.ntt_level_(dig, tb)
+        idx = list(range(l)) + [self.L]
+        dig = torch.empty(x.shape[:-2] + (l, l + 1, self.n), dtype=torch.int64)
         for d in range(l):
-            # digit d: residues mod q_d in [0, q_d), lifted to every limb
             c = self.backend.ntt(x[..., d, :], d, inverse=True)
             if gt is not None:
                 c = self._coeff_automorphism(c, self._q(d), gt)
             for j, i in enumerate(idx):
-                q = self._q(i)
-                dig = self.backend.ntt(torch.remainder(c, q), i)
-                acc0[..., j, :] = torch.remainder(
-                    acc0[..., j, :] + self.backend.modmul(
-                        dig, key[d, 0, i].expand_as(dig).contiguous(), i), q)
-                acc1[..., j, :] = torch.remainder(
-                    acc1[..., j, :] + self.backend.modmul(
-                        dig, key[d, 1, i].expand_as(dig).contiguous(), i), q)
-        return self._moddown_level(acc0, acc1, l)
+                dig[..., d, j, :] = self.backend.ntt(
+                    torch.remainder(c, self._q(i)), i)
+        return dig
 
-    def _moddown_level(self, acc0: torch.Tensor, acc1: torch.Tensor, l: int):
+    def _keyswitch(self, x: torch.Tensor, key: torch.Tensor, l: int,
+                   g: Optional[int] = None):
+        """Level-aware hybrid key-switch of NTT-form x [..., l, n] (l <= L
+        chain limbs) through `key` [L, 2, L+1, n]; returns (ks0, ks1), each
+        [..., l, n]. Uses digits 0..l-1 of the key over the limbs
+        {q_0..q_{l-1}, P}. With g given, switches sigma_g(x) instead. The one
+        key-switch of relinearization (mul_ct) and rotations.
+
+        GPU: the digit launches (_hoist_digits), ONE inner-product kernel over
+        all digits x limbs, then the fused mod-down (_moddown)."""
+        if tuple(key.shape) != (self.L, 2, self.L + 1, self.n):
+            raise ValueError(
+                f"switching key must be [{self.L}, 2, {self.L + 1}, {self.n}], "
+                f"got {tuple(key.shape)}")
+        gt = None if g is None else self._galois_tables(g)
+        dig = self._hoist_digits(x, l, gt)             # [..., l, l+1, n]
+        if self.device.type == "cuda":
+            be = self.backend
+            tb = be.level_tables(l)
+            acc0, acc1 = be._C.ks_inner(dig, self._key_at_level(key, l), tb.qs,
+                                        tb.ratio_words, l, l + 1, self.n)
+            return self._moddown(acc0, acc1, l)
+        acc = torch.empty((2,) + x.shape[:-2] + (l + 1, self.n),
+                          dtype=torch.int64)
+        for c in range(2):
+            for j, i in enumerate(list(range(l)) + [self.L]):
+                acc[c, ..., j, :] = self._dot_mod(
+                    dig[..., j, :], key[:l, c, i], self._q(i), dim=-2)
+        return self._moddown(acc[0], acc[1], l)
+
+    def _moddown(self, acc0: torch.Tensor, acc1: torch.Tensor, l: int):
         """Mod-down by P of the key-switch accumulators [..., l+1, n] over
         the limbs {q_0..q_{l-1}, P} (P at position l) -> (ks0, ks1), each
         [..., l, n]. Any leading shape: a batch of Galois elements goes
@@ -1381,7 +1338,7 @@ class CKKSContext:
         domain, where sigma_g is a pure permutation."""
         l = data.shape[-2]
         gt = self._galois_tables(g)
-        ks0, ks1 = self._keyswitch_level(data[..., 1, :, :], key, l, g=g)
+        ks0, ks1 = self._keyswitch(data[..., 1, :, :], key, l, g=g)
         if self.device.type == "cuda":
             be = self.backend
             if self._galois_fused():
@@ -1499,36 +1456,6 @@ class CKKSContext:
     # by q_d there, both are congruent to sigma_g(c) mod q_d with |digit| <
     # q_d, so the result is a valid rotation under the same noise bound but
     # not bit-identical to rotate_data's.
-    @staticmethod
-    def _dot_mod(a: torch.Tensor, b: torch.Tensor, q: int, dim: int) -> torch.Tensor:
-        """Exact sum over `dim` of a * b mod q (broadcasting, python ints):
-        the CPU oracle's inner product."""
-        r = (a.cpu().numpy().astype(object)
-             * b.cpu().numpy().astype(object)).sum(axis=dim) % q
-        return torch.from_numpy(r.astype(np.int64))
-
-    def _hoist_digits(self, c1: torch.Tensor, l: int) -> torch.Tensor:
-        """NTT-form key-switch digits of c1 [..., l, n] with no automorphism:
-        D[.., d, j, :] = NTT(c_d mod q_j) over the limbs {q_0..q_{l-1}, P},
-        c_d = INTT(c1[.., d, :]) in [0, q_d). Returns [..., l, l+1, n]."""
-        if c1.shape[-2] != l or not 1 <= l <= self.L:
-            raise ValueError(f"expected [.., {l}, n] with 1 <= l <= {self.L}, "
-                             f"got {tuple(c1.shape)}")
-        if self.device.type == "cuda":
-            be = self.backend
-            tb = be.level_tables(l)
-            c = be.ntt_all(c1, inverse=True)
-            dig = be._C.bcast_center_mod(c, 0, tb.qs, tb.ratio_words, l + 1)
-            return be.ntt_level_(dig, tb)
-        idx = list(range(l)) + [self.L]
-        dig = torch.empty(c1.shape[:-2] + (l, l + 1, self.n), dtype=torch.int64)
-        for d in range(l):
-            c = self.backend.ntt(c1[..., d, :], d, inverse=True)
-            for j, i in enumerate(idx):
-                dig[..., d, j, :] = self.backend.ntt(
-                    torch.remainder(c, self._q(i)), i)
-        return dig
-
     def _galois_stack(self, elements: Sequence[int], gk, l: int):
         """(keys [G, l, 2, l+1, n], perm32 [G, n], perm [G, n]) of the given
         Galois elements at level l, stacked once per (elements, level) and
@@ -1620,7 +1547,7 @@ class CKKSContext:
             be = self.backend
             acc0, acc1 = be.ks_inner_hoisted(dig, keys, perm32,
                                              be.level_tables(l))
-            ks0, ks1 = self._moddown_level(acc0, acc1, l)
+            ks0, ks1 = self._moddown(acc0, acc1, l)
             return be.galois_perm_add_many(flat, ks0, ks1, perm32)
         G, R, n = len(elements), flat.shape[0], self.n
         idx = list(range(l)) + [self.L]
@@ -1631,7 +1558,7 @@ class CKKSContext:
                 for t, i in enumerate(idx):
                     acc[c, j, :, t] = self._dot_mod(
                         dp[:, :, t], keys[j, :, c, t], self._q(i), dim=1)
-        ks0, ks1 = self._moddown_level(acc[0], acc[1], l)
+        ks0, ks1 = self._moddown(acc[0], acc[1], l)
         c0 = torch.stack([flat[:, 0].index_select(-1, perm[j])
                           for j in range(G)])             # [G, R, l, n]
         return torch.stack([self._modadd(c0, ks0, list(range(l))), ks1], dim=2)

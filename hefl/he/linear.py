@@ -143,7 +143,7 @@ class LinearTransform:
                     ctx.backend.level_tables(l))
             else:
                 acc0, acc1 = self._inner_cpu(dig, keys, perm)
-            ks0, ks1 = ctx._moddown_level(acc0, acc1, l)
+            ks0, ks1 = ctx._moddown(acc0, acc1, l)
         else:                                              # step 0 only
             ks0 = torch.zeros((R, l, n), dtype=torch.int64, device=ctx.device)
             ks1 = torch.zeros_like(ks0)

@@ -9,7 +9,7 @@ import torch
 
 import hefl
 from hefl.config import HEConfig
-from hefl.he.ckks import CKKSContext, CtxtTensor
+from hefl.he.ckks import CKKSContext, Ciphertext, CtxtTensor
 from hefl.he.ntt_cpu import NttTables, fwd_ntt, inv_ntt
 from hefl.he.primes import gen_prime_chain
 
@@ -289,3 +289,42 @@ def test_gpu_mul_ct_relin_matches_cpu_context():
     assert np.abs(og - ref).max() < 1e-2
     # same-seed contexts produce numerically equal results end to end
     assert np.abs(og - out_c).max() < 1e-3
+
+
+@pytest.fixture(scope="module")
+def mul_ct_pair():
+    """CPU and GPU contexts of one L = 4 chain with equal relin keys, and
+    two CPU-encrypted ciphertexts at level 4 and (one CPU rescale) level 3."""
+    cfg = HEConfig(m=512, scale_bits=26, q_bits=(55, 26, 26, 26), seed=21)
+    cpu = CKKSContext(cfg, device="cpu")
+    gpu = CKKSContext(cfg, device="cuda")
+    kp_c = cpu.keygen()
+    kp_g = gpu.keygen()
+    assert torch.equal(kp_c.sk, kp_g.sk.cpu())
+    rlk_c = cpu.relin_keygen(kp_c.sk)
+    rlk_g = gpu.relin_keygen(kp_g.sk)
+    assert torch.equal(rlk_c, rlk_g.cpu())
+    a = cpu.encrypt(cpu.encode(np.linspace(-1, 1, cfg.m // 2)), kp_c.pk)
+    b = cpu.encrypt(cpu.encode(np.linspace(0.5, -0.5, cfg.m // 2)), kp_c.pk)
+    cts = {4: (a, b), 3: (cpu.rescale(a), cpu.rescale(b))}
+    return cpu, gpu, rlk_c, rlk_g, cts
+
+
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("level", [4, 3])
+def test_gpu_mul_ct_bit_identical_to_cpu(mul_ct_pair, level, B):
+    """ct_mul + the level-aware key-switch on the device against the exact
+    CPU context from the SAME ciphertext integers (encrypted on the CPU,
+    copied across), at the top level and one below, with a [B, 2, l, n]
+    first operand against an unbatched second one."""
+    cpu, gpu, rlk_c, rlk_g, cts = mul_ct_pair
+    a, b = cts[level]
+    assert a.level == level
+    rows = [a.data, b.data, cpu.add(a, a).data][:B]
+    batch = Ciphertext(torch.stack(rows), a.scale)
+    want = cpu.mul_ct(batch, b, rlk_c)
+    got = gpu.mul_ct(Ciphertext(batch.data.cuda(), a.scale),
+                     Ciphertext(b.data.cuda(), b.scale), rlk_g)
+    assert got.data.shape == (B, 2, level, cpu.n)
+    assert got.scale == want.scale
+    assert torch.equal(got.data.cpu(), want.data)
