@@ -64,6 +64,18 @@ std::vector<torch::Tensor> lt_inner(torch::Tensor dig, torch::Tensor keys,
 torch::Tensor lt_finish(torch::Tensor ct, torch::Tensor ks0, torch::Tensor ks1,
                         torch::Tensor pt, torch::Tensor perm, int64_t z0,
                         torch::Tensor qs, torch::Tensor ratios);
+int64_t bsgs_baby_tile();
+int64_t bsgs_flush_terms();
+torch::Tensor bsgs_mac(torch::Tensor ct, torch::Tensor rot, torch::Tensor pt,
+                       torch::Tensor goff, torch::Tensor bidx, bool has0,
+                       torch::Tensor qs, torch::Tensor ratios);
+std::vector<torch::Tensor> bsgs_giant_inner(torch::Tensor dig,
+                                            torch::Tensor keys,
+                                            torch::Tensor perm,
+                                            torch::Tensor qs,
+                                            torch::Tensor ratios);
+torch::Tensor bsgs_finish(torch::Tensor u, torch::Tensor ks0, torch::Tensor ks1,
+                          torch::Tensor perm, int64_t z0, torch::Tensor qs);
 
 // fft.hip
 torch::Tensor fft_encode(torch::Tensor vals, torch::Tensor tw_enc,
@@ -227,6 +239,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "(acc0, acc1) [R, Lp, n]");
     m.def("lt_finish", &lt_finish,
           "linear transform: ks + sum_g pt_g * c0[perm_g], step-0 term of c1");
+    m.def("bsgs_mac", &bsgs_mac,
+          "BSGS multiply-accumulate: u[g] = sum_j pt[g+j] * baby_j, "
+          "[Ng, R, 2, L, n]");
+    m.def("bsgs_giant_inner", &bsgs_giant_inner,
+          "key-switch inner product of every keyed giant's own digits, "
+          "summed over giants: (acc0, acc1) [R, Lp, n]");
+    m.def("bsgs_finish", &bsgs_finish,
+          "BSGS finish: ks + sum_g u[g, c0][perm_g], giant-0 term of c1");
+    m.attr("BSGS_BABY_TILE") = bsgs_baby_tile();
+    m.attr("BSGS_FLUSH_TERMS") = bsgs_flush_terms();
     m.def("fft_encode", &fft_encode,
           "CKKS special-FFT encode: f64 slots -> int64 coeffs");
     m.def("fft_decode", &fft_decode,

@@ -36,6 +36,8 @@
 //                                            from one digit decomposition
 //   lt_inner / lt_finish kernels             ct x plaintext-matrix: diagonals
 //                                            summed before a single mod-down
+//   bsgs_mac / bsgs_giant_inner / bsgs_finish  the same transform by baby and
+//                                            giant steps: ~2 sqrt(G) keys
 //
 // Structure per row of length n (n = 2^6 .. 2^15):
 //  * stages whose butterfly span exceeds NBLK run in a strided global-memory
@@ -1272,6 +1274,280 @@ __global__ void lt_finish_kernel(const int64_t* __restrict__ ct,
     }
 }
 
+// ---------------------------------------------------------------------------
+// Baby-step/giant-step linear transform (hefl/he/linear.py, bsgs=...). A
+// diagonal step k = g + j (baby j = k mod n1, giant g): the babies rot_j(ct)
+// are hoisted rotations, bsgs_mac weights them into one ciphertext-shaped sum
+// u[g] per giant, bsgs_giant_inner key-switches all u[g != 0] into ONE
+// accumulator pair (one mod-down for every giant) and bsgs_finish adds the
+// permuted c0 parts.
+//
+// Lazy reduction: residues are < q < 2^60, so a product is < 2^120 and
+// kBsgsFlush = 128 of them sum below 2^127. A flush leaves a residue < 2^60
+// in the accumulator, so it never holds more than 2^60 + 2^127 < 2^128, which
+// is all barrett_red128 asks of its argument (qhat = floor(z * ratio / 2^128)
+// is the quotient or one less for any z < 2^128). One Barrett per flush
+// replaces one per term.
+// ---------------------------------------------------------------------------
+
+constexpr int kBsgsFlush = 128;     // terms per 128-bit accumulator flush
+constexpr int kBsgsBabyTile = 32;   // babies resident in LDS at a time
+constexpr int kBsgsWaves = kThreads / 64;
+
+struct Acc128 {
+    uint64_t lo, hi;
+};
+
+__device__ __forceinline__ void acc128_mad(Acc128& a, uint64_t x, uint64_t y) {
+    const uint64_t lo = x * y;
+    a.lo += lo;
+    a.hi += __umul64hi(x, y) + (a.lo < lo);
+}
+
+// u[g, r, c, i, k] = sum_{t in [goff[g], goff[g+1])} pt[t, i, k] *
+//                    baby_{bidx[t]}[r, c, i, k]   mod q_i
+// Baby b is ct itself when has0 and b == 0 (read in place), else
+// rot[b - has0]; ct is [R, 2, L, n], rot [Nb - has0, R, 2, L, n], pt
+// [T, L, n] sorted by giant, u [Ng, R, 2, L, n].
+//
+// A block owns one (row r, limb i, tile of 64 * V coefficients) and one of
+// gridDim.y giant groups. Babies pass through LDS kBsgsBabyTile at a time:
+// both components of the tile's babies at the block's coefficients are staged
+// once ([tile, 2, 64] Vecs, 32 KiB * V) and reused by every giant. Lanes map
+// to coefficients; the waves split the giants (stride kBsgsWaves *
+// gridDim.y), each streaming its giants' plaintext rows with one coalesced
+// 8 * V-byte load per lane and term, so a plaintext word is read once and a
+// baby word once per giant group. With more babies than one tile the later
+// tiles add into u; the same lane wrote the word it reads back.
+// goff / bidx are device data: term ranges are clamped to [0, T] and a term
+// whose baby lies outside the resident tile is skipped, so no index leaves
+// its tensor whatever they hold.
+template <int V>
+__global__ void __launch_bounds__(kThreads)
+bsgs_mac_kernel(const int64_t* __restrict__ ct,
+                const int64_t* __restrict__ rot,
+                const int64_t* __restrict__ pt,
+                const int32_t* __restrict__ goff,
+                const int32_t* __restrict__ bidx,
+                int64_t* __restrict__ u, int64_t n, int L, int64_t R, int Ng,
+                int Nb, int T, int has0, int ktiles,
+                const int64_t* __restrict__ qs,
+                const int64_t* __restrict__ ratios) {
+    using Vec = I64Vec<V>;
+    extern __shared__ __align__(16) unsigned char bsgs_lds[];
+    Vec* tile = reinterpret_cast<Vec*>(bsgs_lds);   // [tn, 2, 64]
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int kt = blockIdx.x % ktiles;
+    const int i = (blockIdx.x / ktiles) % L;
+    const int64_t r = blockIdx.x / ((int64_t)ktiles * L);
+    const int64_t k0 = ((int64_t)kt * 64 + lane) * V;
+    const bool live = k0 < n;                       // n < 64 * V: idle lanes
+    const int64_t Ln = (int64_t)L * n;
+    const int64_t ct_off = r * 2 * Ln + (int64_t)i * n + k0;   // component 0
+    const uint64_t q = (uint64_t)qs[i];
+    const uint64_t r0 = (uint64_t)ratios[2 * i];
+    const uint64_t r1 = (uint64_t)ratios[2 * i + 1];
+
+    for (int b_lo = 0; b_lo < Nb; b_lo += kBsgsBabyTile) {
+        const int tn = min(kBsgsBabyTile, Nb - b_lo);
+        if (b_lo) __syncthreads();                  // last tile fully consumed
+        for (int e = threadIdx.x; e < tn * 128; e += kThreads) {
+            const int el = e & 63, c = (e >> 6) & 1, b = b_lo + (e >> 7);
+            const int64_t ek0 = ((int64_t)kt * 64 + el) * V;
+            if (ek0 < n) {
+                const int64_t off = r * 2 * Ln + c * Ln + (int64_t)i * n + ek0;
+                const int64_t* src = (has0 && b == 0)
+                    ? ct + off
+                    : rot + (int64_t)(b - has0) * R * 2 * Ln + off;
+                tile[e] = *reinterpret_cast<const Vec*>(src);
+            }
+        }
+        __syncthreads();
+        if (!live) continue;
+        for (int g = blockIdx.y * kBsgsWaves + wave; g < Ng;
+             g += kBsgsWaves * gridDim.y) {
+            const int t_lo = max(goff[g], 0), t_hi = min(goff[g + 1], T);
+            Acc128 a0[V], a1[V];
+#pragma unroll
+            for (int k = 0; k < V; ++k) a0[k] = a1[k] = Acc128{0, 0};
+            int pending = 0;
+            bool any = false;
+            for (int t = t_lo; t < t_hi; ++t) {
+                const unsigned bb = (unsigned)(bidx[t] - b_lo);
+                if (bb >= (unsigned)tn) continue;
+                any = true;
+                const Vec p = *reinterpret_cast<const Vec*>(
+                    pt + (int64_t)t * Ln + (int64_t)i * n + k0);
+                const Vec x0 = tile[bb * 128 + lane];
+                const Vec x1 = tile[bb * 128 + 64 + lane];
+#pragma unroll
+                for (int k = 0; k < V; ++k) {
+                    acc128_mad(a0[k], (uint64_t)p.v[k], (uint64_t)x0.v[k]);
+                    acc128_mad(a1[k], (uint64_t)p.v[k], (uint64_t)x1.v[k]);
+                }
+                if (++pending == kBsgsFlush) {
+                    pending = 0;
+#pragma unroll
+                    for (int k = 0; k < V; ++k) {
+                        a0[k] = Acc128{barrett_red128(a0[k].lo, a0[k].hi, q,
+                                                      r0, r1), 0};
+                        a1[k] = Acc128{barrett_red128(a1[k].lo, a1[k].hi, q,
+                                                      r0, r1), 0};
+                    }
+                }
+            }
+            if (b_lo && !any) continue;             // nothing to add to u
+            int64_t* dst = u + (int64_t)g * R * 2 * Ln + ct_off;
+            Vec y0, y1;
+            if (b_lo) {
+                y0 = *reinterpret_cast<const Vec*>(dst);
+                y1 = *reinterpret_cast<const Vec*>(dst + Ln);
+            }
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                uint64_t v0 = barrett_red128(a0[k].lo, a0[k].hi, q, r0, r1);
+                uint64_t v1 = barrett_red128(a1[k].lo, a1[k].hi, q, r0, r1);
+                if (b_lo) {
+                    v0 = addmod_u64(v0, (uint64_t)y0.v[k], q);
+                    v1 = addmod_u64(v1, (uint64_t)y1.v[k], q);
+                }
+                y0.v[k] = (int64_t)v0;
+                y1.v[k] = (int64_t)v1;
+            }
+            *reinterpret_cast<Vec*>(dst) = y0;
+            *reinterpret_cast<Vec*>(dst + Ln) = y1;
+        }
+    }
+}
+
+// Key-switch inner product of the keyed giants, summed over them before the
+// mod-down:
+//   acc_c[r, i, k] = sum_g sum_d dig[g, r, d, i, perm[g, k]] * keys[g, d, c, i, k]
+// mod q_i. The gather form of ks_inner_hoisted_kernel, but every giant has
+// its OWN digits, dig [G, R, D, Lp, n] (the digits of u[g]), and the G * D
+// products go into one lazily reduced 128-bit sum per output. keys is
+// [G, D, 2, Lp, n], perm int32 [G, n]; acc0 / acc1 are [R, Lp, n].
+template <int V>
+__global__ void bsgs_giant_inner_kernel(const int64_t* __restrict__ dig,
+                                        const int64_t* __restrict__ keys,
+                                        const int32_t* __restrict__ perm,
+                                        int64_t* __restrict__ acc0,
+                                        int64_t* __restrict__ acc1,
+                                        int64_t total_vec, int64_t n, int D,
+                                        int Lp, int64_t R, int G,
+                                        const int64_t* __restrict__ qs,
+                                        const int64_t* __restrict__ ratios) {
+    using Vec = I64Vec<V>;
+    const int64_t Lpn = (int64_t)Lp * n;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+         t < total_vec; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = t * V;              // index into acc's [R, Lp, n]
+        const int64_t k0 = o % n;
+        const int i = (int)((o / n) % Lp);
+        const int64_t row = o / Lpn;
+        const uint64_t q = (uint64_t)qs[i];
+        const uint64_t r0 = (uint64_t)ratios[2 * i];
+        const uint64_t r1 = (uint64_t)ratios[2 * i + 1];
+        Acc128 a0[V], a1[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) a0[k] = a1[k] = Acc128{0, 0};
+        int pending = 0;
+        for (int g = 0; g < G; ++g) {
+            int64_t src[V];
+#pragma unroll
+            for (int k = 0; k < V; ++k)
+                src[k] = (int64_t)perm[(int64_t)g * n + k0 + k] & (n - 1);
+            const int64_t* dig_row =
+                dig + ((int64_t)g * R + row) * D * Lpn + (int64_t)i * n;
+            const int64_t* key_row =
+                keys + (int64_t)g * D * 2 * Lpn + (int64_t)i * n + k0;
+            for (int d = 0; d < D; ++d) {
+                const Vec b0 = *reinterpret_cast<const Vec*>(
+                    key_row + (int64_t)d * 2 * Lpn);
+                const Vec b1 = *reinterpret_cast<const Vec*>(
+                    key_row + (int64_t)d * 2 * Lpn + Lpn);
+#pragma unroll
+                for (int k = 0; k < V; ++k) {
+                    const uint64_t x =
+                        (uint64_t)dig_row[(int64_t)d * Lpn + src[k]];
+                    acc128_mad(a0[k], x, (uint64_t)b0.v[k]);
+                    acc128_mad(a1[k], x, (uint64_t)b1.v[k]);
+                }
+                if (++pending == kBsgsFlush) {
+                    pending = 0;
+#pragma unroll
+                    for (int k = 0; k < V; ++k) {
+                        a0[k] = Acc128{barrett_red128(a0[k].lo, a0[k].hi, q,
+                                                      r0, r1), 0};
+                        a1[k] = Acc128{barrett_red128(a1[k].lo, a1[k].hi, q,
+                                                      r0, r1), 0};
+                    }
+                }
+            }
+        }
+        Vec y0, y1;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            y0.v[k] = (int64_t)barrett_red128(a0[k].lo, a0[k].hi, q, r0, r1);
+            y1.v[k] = (int64_t)barrett_red128(a1[k].lo, a1[k].hi, q, r0, r1);
+        }
+        *reinterpret_cast<Vec*>(acc0 + o) = y0;
+        *reinterpret_cast<Vec*>(acc1 + o) = y1;
+    }
+}
+
+// BSGS finish: the giant rotations' c0 parts, gathered from u through the
+// giants' permutations, and the giant-0 sum's c1 part added to the mod-down
+// outputs. u is [Ng, R, 2, L, n], ks0 / ks1 [R, L, n], perm int32 [Ng, n]
+// (the identity row for giant 0); z0 is giant 0's index or -1:
+//   out[r, 0, i, k] = ks0[r, i, k] + sum_g u[g, r, 0, i, perm[g, k]]
+//   out[r, 1, i, k] = ks1[r, i, k] + u[z0, r, 1, i, k]
+// Adds only; no multiply.
+template <int V>
+__global__ void bsgs_finish_kernel(const int64_t* __restrict__ u,
+                                   const int64_t* __restrict__ ks0,
+                                   const int64_t* __restrict__ ks1,
+                                   const int32_t* __restrict__ perm,
+                                   int64_t* __restrict__ out,
+                                   int64_t total_vec, int64_t n, int L,
+                                   int64_t R, int Ng, int z0,
+                                   const int64_t* __restrict__ qs) {
+    using Vec = I64Vec<V>;
+    const int64_t Ln = (int64_t)L * n;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+         t < total_vec; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = t * V;              // index into ks0's [R, L, n]
+        const int64_t k0 = o % n;
+        const int l = (int)((o / n) % L);
+        const int64_t row = o / Ln;
+        const uint64_t q = (uint64_t)qs[l];
+        const int64_t c0_row = row * 2 * Ln + (int64_t)l * n;
+        Vec y0 = *reinterpret_cast<const Vec*>(ks0 + o);
+        Vec y1 = *reinterpret_cast<const Vec*>(ks1 + o);
+        for (int g = 0; g < Ng; ++g) {
+            const int64_t* ug = u + (int64_t)g * R * 2 * Ln + c0_row;
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                const int64_t src =
+                    (int64_t)perm[(int64_t)g * n + k0 + k] & (n - 1);
+                y0.v[k] = (int64_t)addmod_u64((uint64_t)y0.v[k],
+                                              (uint64_t)ug[src], q);
+            }
+        }
+        if (z0 >= 0) {
+            const Vec c1 = *reinterpret_cast<const Vec*>(
+                u + (int64_t)z0 * R * 2 * Ln + c0_row + Ln + k0);
+#pragma unroll
+            for (int k = 0; k < V; ++k)
+                y1.v[k] = (int64_t)addmod_u64((uint64_t)y1.v[k],
+                                              (uint64_t)c1.v[k], q);
+        }
+        *reinterpret_cast<Vec*>(out + c0_row + k0) = y0;
+        *reinterpret_cast<Vec*>(out + c0_row + Ln + k0) = y1;
+    }
+}
+
 inline bool aligned16(const void* p) {
     return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
 }
@@ -2052,6 +2328,195 @@ torch::Tensor lt_finish(torch::Tensor ct, torch::Tensor ks0, torch::Tensor ks1,
                            out.data_ptr<int64_t>(), tv, n, (int)L, (int)G,
                            (int)z0, qs.data_ptr<int64_t>(),
                            ratios.data_ptr<int64_t>());
+    }
+    return out;
+}
+
+int64_t bsgs_baby_tile() { return kBsgsBabyTile; }
+int64_t bsgs_flush_terms() { return kBsgsFlush; }
+
+// BSGS multiply-accumulate. ct [R, 2, L, n]; rot [Nb', R, 2, L, n], the
+// non-zero baby rotations of ct (Nb' may be 0); has0 says that baby 0 (ct
+// itself, read in place) leads the baby list, so Nb = Nb' + has0; pt
+// [T, L, n] the diagonals sorted by giant, goff int32 [Ng + 1] their offsets
+// per giant, bidx int32 [T] each diagonal's baby index -> u [Ng, R, 2, L, n].
+torch::Tensor bsgs_mac(torch::Tensor ct, torch::Tensor rot, torch::Tensor pt,
+                       torch::Tensor goff, torch::Tensor bidx, bool has0,
+                       torch::Tensor qs, torch::Tensor ratios) {
+    CHECK_CUDA_OK(ct);
+    CHECK_CUDA_OK(rot);
+    CHECK_CUDA_OK(pt);
+    CHECK_CUDA_OK(goff);
+    CHECK_CUDA_OK(bidx);
+    CHECK_CUDA_OK(qs);
+    CHECK_CUDA_OK(ratios);
+    ct = ct.contiguous();
+    rot = rot.contiguous();
+    pt = pt.contiguous();
+    goff = goff.contiguous();
+    bidx = bidx.contiguous();
+    TORCH_CHECK(qs.is_contiguous() && ratios.is_contiguous(),
+                "prime tables must be contiguous");
+    TORCH_CHECK(ct.dtype() == torch::kInt64 && rot.dtype() == torch::kInt64 &&
+                pt.dtype() == torch::kInt64 && qs.dtype() == torch::kInt64 &&
+                ratios.dtype() == torch::kInt64 &&
+                goff.dtype() == torch::kInt32 && bidx.dtype() == torch::kInt32,
+                "int64 tensors and int32 goff / bidx expected");
+    TORCH_CHECK(ct.dim() == 4 && ct.size(1) == 2, "ct must be [R, 2, L, n]");
+    const int64_t R = ct.size(0), L = ct.size(2), n = ct.size(3);
+    TORCH_CHECK(n >= 1 && (n & (n - 1)) == 0, "n must be a power of two");
+    TORCH_CHECK(R >= 1 && L >= 1 && qs.numel() >= L &&
+                ratios.numel() >= 2 * L, "limb count exceeds the prime table");
+    TORCH_CHECK(rot.dim() == 5 && rot.size(1) == R && rot.size(2) == 2 &&
+                rot.size(3) == L && rot.size(4) == n,
+                "rot must be [Nb', R, 2, L, n]");
+    const int64_t Nb = rot.size(0) + (has0 ? 1 : 0);
+    TORCH_CHECK(Nb >= 1, "no babies: rot is empty and has0 is false");
+    TORCH_CHECK(pt.dim() == 3 && pt.size(0) >= 1 && pt.size(1) == L &&
+                pt.size(2) == n, "pt must be [T, L, n]");
+    const int64_t T = pt.size(0);
+    TORCH_CHECK(bidx.dim() == 1 && bidx.size(0) == T, "bidx must be int32 [T]");
+    TORCH_CHECK(goff.dim() == 1 && goff.size(0) >= 2,
+                "goff must be int32 [Ng + 1]");
+    const int64_t Ng = goff.size(0) - 1;
+    TORCH_CHECK(T <= INT32_MAX && Nb <= INT32_MAX && Ng <= INT32_MAX,
+                "too many diagonals");
+    auto u = torch::empty({Ng, R, 2, L, n}, ct.options());
+    auto stream = at::cuda::getCurrentCUDAStream();
+    const bool vec2 = n % 2 == 0 && aligned16(ct.data_ptr<int64_t>()) &&
+                      aligned16(rot.data_ptr<int64_t>()) &&
+                      aligned16(pt.data_ptr<int64_t>()) &&
+                      aligned16(u.data_ptr<int64_t>());
+    const int V = vec2 ? 2 : 1;
+    const int64_t ktiles = (n + 64 * V - 1) / (64 * V);
+    const int64_t bx = R * L * ktiles;
+    TORCH_CHECK(bx <= INT32_MAX, "batch too large for gridDim.x");
+    // a small batch leaves CUs idle: split the giants over gridDim.y until
+    // there are ~1024 blocks or one giant per wave (babies are re-staged per
+    // split, plaintexts are still read once)
+    const int64_t by = std::max<int64_t>(1, std::min<int64_t>(
+        (1024 + bx - 1) / bx, (Ng + kBsgsWaves - 1) / kBsgsWaves));
+    const size_t lds = (size_t)std::min<int64_t>(Nb, kBsgsBabyTile) * 128 * 8 * V;
+    const dim3 grid((unsigned)bx, (unsigned)by, 1);
+    if (vec2) {
+        hipLaunchKernelGGL(bsgs_mac_kernel<2>, grid, dim3(kThreads), lds,
+                           stream, ct.data_ptr<int64_t>(),
+                           rot.data_ptr<int64_t>(), pt.data_ptr<int64_t>(),
+                           goff.data_ptr<int32_t>(), bidx.data_ptr<int32_t>(),
+                           u.data_ptr<int64_t>(), n, (int)L, R, (int)Ng,
+                           (int)Nb, (int)T, (int)has0, (int)ktiles,
+                           qs.data_ptr<int64_t>(), ratios.data_ptr<int64_t>());
+    } else {
+        hipLaunchKernelGGL(bsgs_mac_kernel<1>, grid, dim3(kThreads), lds,
+                           stream, ct.data_ptr<int64_t>(),
+                           rot.data_ptr<int64_t>(), pt.data_ptr<int64_t>(),
+                           goff.data_ptr<int32_t>(), bidx.data_ptr<int32_t>(),
+                           u.data_ptr<int64_t>(), n, (int)L, R, (int)Ng,
+                           (int)Nb, (int)T, (int)has0, (int)ktiles,
+                           qs.data_ptr<int64_t>(), ratios.data_ptr<int64_t>());
+    }
+    return u;
+}
+
+// dig [G, R, D, Lp, n] (the hoisted digits of each keyed giant's u[g]) x keys
+// [G, D, 2, Lp, n] under perm [G, n], summed over G -> (acc0, acc1) each
+// [R, Lp, n], ready for one mod-down.
+std::vector<torch::Tensor> bsgs_giant_inner(torch::Tensor dig,
+                                            torch::Tensor keys,
+                                            torch::Tensor perm,
+                                            torch::Tensor qs,
+                                            torch::Tensor ratios) {
+    dig = dig.contiguous();
+    keys = keys.contiguous();
+    perm = perm.contiguous();
+    TORCH_CHECK(dig.dim() == 5 && dig.size(0) == keys.size(0),
+                "dig must be [G, R, D, Lp, n] with one digit tensor per key");
+    check_hoisted_args(dig[0], keys, perm, qs, ratios);
+    const int64_t G = dig.size(0), R = dig.size(1), D = dig.size(2);
+    const int64_t Lp = dig.size(3), n = dig.size(4);
+    auto acc0 = torch::empty({R, Lp, n}, dig.options());
+    auto acc1 = torch::empty({R, Lp, n}, dig.options());
+    const int64_t total = acc0.numel();
+    auto stream = at::cuda::getCurrentCUDAStream();
+    // dig is only gathered (8-byte reads, any alignment)
+    const bool vec2 = n % 2 == 0 && aligned16(keys.data_ptr<int64_t>()) &&
+                      aligned16(acc0.data_ptr<int64_t>()) &&
+                      aligned16(acc1.data_ptr<int64_t>());
+    const int64_t tv = vec2 ? total / 2 : total;
+    int blocks = (int)std::min<int64_t>((tv + kThreads - 1) / kThreads, 4096);
+    if (vec2) {
+        hipLaunchKernelGGL(bsgs_giant_inner_kernel<2>, dim3(blocks),
+                           dim3(kThreads), 0, stream, dig.data_ptr<int64_t>(),
+                           keys.data_ptr<int64_t>(), perm.data_ptr<int32_t>(),
+                           acc0.data_ptr<int64_t>(), acc1.data_ptr<int64_t>(),
+                           tv, n, (int)D, (int)Lp, R, (int)G,
+                           qs.data_ptr<int64_t>(), ratios.data_ptr<int64_t>());
+    } else {
+        hipLaunchKernelGGL(bsgs_giant_inner_kernel<1>, dim3(blocks),
+                           dim3(kThreads), 0, stream, dig.data_ptr<int64_t>(),
+                           keys.data_ptr<int64_t>(), perm.data_ptr<int32_t>(),
+                           acc0.data_ptr<int64_t>(), acc1.data_ptr<int64_t>(),
+                           tv, n, (int)D, (int)Lp, R, (int)G,
+                           qs.data_ptr<int64_t>(), ratios.data_ptr<int64_t>());
+    }
+    return {acc0, acc1};
+}
+
+// u [Ng, R, 2, L, n] (bsgs_mac's sums), ks0 / ks1 [R, L, n] (the mod-down of
+// bsgs_giant_inner's sums), perm int32 [Ng, n] with the identity row for
+// giant 0, z0 = giant 0's index or -1 -> transformed ciphertext [R, 2, L, n].
+torch::Tensor bsgs_finish(torch::Tensor u, torch::Tensor ks0, torch::Tensor ks1,
+                          torch::Tensor perm, int64_t z0, torch::Tensor qs) {
+    CHECK_CUDA_OK(u);
+    CHECK_CUDA_OK(ks0);
+    CHECK_CUDA_OK(ks1);
+    CHECK_CUDA_OK(perm);
+    CHECK_CUDA_OK(qs);
+    u = u.contiguous();
+    ks0 = ks0.contiguous();
+    ks1 = ks1.contiguous();
+    perm = perm.contiguous();
+    TORCH_CHECK(qs.is_contiguous(), "prime table must be contiguous");
+    TORCH_CHECK(u.dtype() == torch::kInt64 && ks0.dtype() == torch::kInt64 &&
+                ks1.dtype() == torch::kInt64 && qs.dtype() == torch::kInt64 &&
+                perm.dtype() == torch::kInt32,
+                "int64 tensors and an int32 perm expected");
+    TORCH_CHECK(u.dim() == 5 && u.size(0) >= 1 && u.size(2) == 2,
+                "u must be [Ng, R, 2, L, n]");
+    const int64_t Ng = u.size(0), R = u.size(1), L = u.size(3), n = u.size(4);
+    TORCH_CHECK(n >= 1 && (n & (n - 1)) == 0, "n must be a power of two");
+    TORCH_CHECK(R >= 1 && L >= 1 && qs.numel() >= L,
+                "limb count exceeds the prime table");
+    const std::vector<int64_t> ks_sizes = {R, L, n};
+    TORCH_CHECK(ks0.sizes().vec() == ks_sizes && ks1.sizes().vec() == ks_sizes,
+                "ks0 / ks1 must be [R, L, n]");
+    TORCH_CHECK(Ng <= INT32_MAX / n, "too many giants");
+    TORCH_CHECK(perm.dim() == 2 && perm.size(0) == Ng && perm.size(1) == n,
+                "perm must be int32 [Ng, n]");
+    TORCH_CHECK(z0 >= -1 && z0 < Ng, "z0 must index a giant or be -1");
+    auto out = torch::empty({R, 2, L, n}, u.options());
+    const int64_t total = ks0.numel();
+    auto stream = at::cuda::getCurrentCUDAStream();
+    const bool vec2 = n % 2 == 0 && aligned16(u.data_ptr<int64_t>()) &&
+                      aligned16(ks0.data_ptr<int64_t>()) &&
+                      aligned16(ks1.data_ptr<int64_t>()) &&
+                      aligned16(out.data_ptr<int64_t>());
+    const int64_t tv = vec2 ? total / 2 : total;
+    int blocks = (int)std::min<int64_t>((tv + kThreads - 1) / kThreads, 4096);
+    if (vec2) {
+        hipLaunchKernelGGL(bsgs_finish_kernel<2>, dim3(blocks), dim3(kThreads),
+                           0, stream, u.data_ptr<int64_t>(),
+                           ks0.data_ptr<int64_t>(), ks1.data_ptr<int64_t>(),
+                           perm.data_ptr<int32_t>(), out.data_ptr<int64_t>(),
+                           tv, n, (int)L, R, (int)Ng, (int)z0,
+                           qs.data_ptr<int64_t>());
+    } else {
+        hipLaunchKernelGGL(bsgs_finish_kernel<1>, dim3(blocks), dim3(kThreads),
+                           0, stream, u.data_ptr<int64_t>(),
+                           ks0.data_ptr<int64_t>(), ks1.data_ptr<int64_t>(),
+                           perm.data_ptr<int32_t>(), out.data_ptr<int64_t>(),
+                           tv, n, (int)L, R, (int)Ng, (int)z0,
+                           qs.data_ptr<int64_t>());
     }
     return out;
 }

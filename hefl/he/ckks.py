@@ -303,6 +303,31 @@ class GpuBackend:
                                  ks1.contiguous(), pt, perm, int(z0), self.qs,
                                  self.ratio_words)
 
+    # ----- baby-step/giant-step linear transform (linear.py, bsgs=...) -----
+    def bsgs_mac(self, ct: torch.Tensor, rot: torch.Tensor, pt: torch.Tensor,
+                 goff: torch.Tensor, bidx: torch.Tensor,
+                 has0: bool) -> torch.Tensor:
+        """u[g] = sum over giant g's diagonals t of pt[t] * baby_{bidx[t]},
+        [Ng, R, 2, l, n]. ct [R, 2, l, n] is baby 0 when has0 (read in
+        place), rot [Nb', R, 2, l, n] the other babies, pt [T, l, n] sorted
+        by giant with offsets goff int32 [Ng + 1]. One launch."""
+        return self._C.bsgs_mac(ct, rot, pt, goff, bidx, bool(has0), self.qs,
+                                self.ratio_words)
+
+    def bsgs_giant_inner(self, dig: torch.Tensor, keys: torch.Tensor,
+                         perm: torch.Tensor, tb: "LevelTables"):
+        """dig [G, R, l, l+1, n] (each giant's own digits) x keys
+        [G, l, 2, l+1, n] under perm [G, n], summed over G -> (acc0, acc1),
+        each [R, l+1, n]. One launch."""
+        return self._C.bsgs_giant_inner(dig, keys, perm, tb.qs, tb.ratio_words)
+
+    def bsgs_finish(self, u: torch.Tensor, ks0: torch.Tensor,
+                    ks1: torch.Tensor, perm: torch.Tensor,
+                    z0: int) -> torch.Tensor:
+        """(ks0 + sum_g u[g, :, 0][perm_g], ks1 + u[z0, :, 1]) as
+        [R, 2, l, n]; z0 giant 0's index or -1. One launch."""
+        return self._C.bsgs_finish(u, ks0, ks1, perm, int(z0), self.qs)
+
 
 @dataclass
 class LevelTables:
@@ -1575,12 +1600,13 @@ class CKKSContext:
         return [CtxtTensor(d, ct.scale, ct.count, ct.packing) for d in
                 self.rotate_many_data(ct.data, steps, gk, conjugate)]
 
-    def matvec(self, M, ct, gk):
+    def matvec(self, M, ct, gk, bsgs=None):
         """M @ (slots of ct) for a real matrix M [r, c], r, c <= slots: a
         one-shot LinearTransform (hefl/he/linear.py) at ct's level. The
-        result is at scale ct.scale * self.scale, not rescaled."""
+        result is at scale ct.scale * self.scale, not rescaled. bsgs="auto"
+        or a baby-step count n1 selects the baby-step/giant-step form."""
         from .linear import LinearTransform
-        lt = LinearTransform(self, M, level=ct.level)
+        lt = LinearTransform(self, M, level=ct.level, bsgs=bsgs)
         if isinstance(ct, CtxtTensor):
             return lt.apply_tensor(ct, gk)
         return lt.apply(ct, gk)
