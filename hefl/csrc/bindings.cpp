@@ -97,7 +97,8 @@ torch::Tensor conv2d_dgrad(torch::Tensor dy, torch::Tensor w, int64_t stride,
 torch::Tensor conv2d_wgrad(torch::Tensor dy, torch::Tensor x, int64_t stride,
                            int64_t R, int64_t S, int64_t pad, int64_t gkey);
 torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,
-                         bool relu);
+                         bool relu, bool panel);
+bool linear_fwd_panel_ok(torch::Tensor x, torch::Tensor w);
 torch::Tensor linear_dgrad(torch::Tensor dy, torch::Tensor w);
 torch::Tensor linear_wgrad(torch::Tensor dy, torch::Tensor x);
 std::vector<torch::Tensor> maxpool2x2_fwd(torch::Tensor x);
@@ -267,7 +268,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("conv2d_wgrad", &conv2d_wgrad, py::arg("dy"), py::arg("x"),
           py::arg("stride"), py::arg("R"), py::arg("S"), py::arg("pad"),
           py::arg("gkey") = 0);
-    m.def("linear_fwd", &linear_fwd);
+    m.def("linear_fwd", &linear_fwd, py::arg("x"), py::arg("w"), py::arg("b"),
+          py::arg("relu"), py::arg("panel") = true,
+          "y = x.w^T + b; panel=false keeps the one-slab case on the "
+          "direct-from-global kernel");
+    m.def("linear_fwd_panel_ok", &linear_fwd_panel_ok, py::arg("x"),
+          py::arg("w"), "whether linear_fwd runs the whole-K panel kernel");
     m.def("linear_dgrad", &linear_dgrad);
     m.def("linear_wgrad", &linear_wgrad);
     m.def("maxpool2x2_fwd", &maxpool2x2_fwd);

@@ -90,6 +90,9 @@
 //                                  and their backward) in two single-
 //                                  workgroup launches
 //   linear_bwd_pair_kernel         dense dgrad + wgrad in one launch
+//   linear_panel_kernel<VEC>       linear_fwd's one-slab case: whole-K x / w
+//                                  panels to LDS with all loads in flight,
+//                                  then linear_splitk_kernel<1>'s MFMA chain
 //   maxpool_gen_fwd/bwd_kernel     generic k/s/p pooling (ResNet stem)
 //   avgpool_global_fwd/bwd_kernel  global average pool
 //   add_relu_kernel                residual add + ReLU (bf16x8)
@@ -3346,6 +3349,123 @@ __global__ void linear_epilogue_kernel(float* __restrict__ y32,
 }
 
 // ---------------------------------------------------------------------------
+// Whole-K panel forward for linear_fwd's one-slab case (M <= 64, K <= 1024).
+// linear_splitk_kernel<1> runs K/32 dependent k-steps per wave with its
+// fragments loaded straight from global, a few at a time: at fc1's 800 -> 64
+// that is ~7 global round trips back to back on 8 waves. Here one 256-thread
+// block per 16x16 output tile puts every 16-B load of the tile's x panel
+// [16, K] and w panel [16, K] in flight at once, parks them in LDS, and
+// after ONE barrier wave 0 runs the same MFMA chain from LDS: same operand
+// in the same k-slot (k + (lane>>4)*8 + j), k = 0, 32, ... in order, zero
+// padded rows and k-tail, bias after the chain, relu, f2bf — every output
+// bit equals linear_splitk_kernel<1>'s.
+// Rows are padded by 8 elements so the 16 rows of a fragment read spread
+// over the LDS banks (K = 800 is a 1600-B row stride).
+// VEC: K % 8 == 0 and 16-B aligned bases; otherwise 2-B loads, same image.
+// ---------------------------------------------------------------------------
+
+constexpr int LP_KMAX = 1024;
+constexpr int LP_PAD = 8;
+constexpr int LP_SMEM_MAX = 2 * 16 * (LP_KMAX + LP_PAD) * 2;  // bytes
+
+template <bool VEC>
+__global__ void __launch_bounds__(TPB)
+linear_panel_kernel(const unsigned short* __restrict__ x,
+                    const unsigned short* __restrict__ w,
+                    const float* __restrict__ bias,
+                    unsigned short* __restrict__ yout, int M, int N, int K,
+                    int relu) {
+    extern __shared__ __align__(16) unsigned short lp_smem[];
+    const int tid = threadIdx.x;
+    const int m0 = blockIdx.x * 16;
+    const int n0 = blockIdx.y * 16;
+    const int Kp = (K + 31) & ~31;
+    const int ld = Kp + LP_PAD;
+    const int nch = Kp >> 3;             // 8-element chunks per padded row
+    unsigned short* xs = lp_smem;
+    unsigned short* ws = lp_smem + 16 * ld;
+    const int r = tid >> 4;              // panel row 0..15
+    const int c16 = tid & 15;            // chunk within a group of 16
+    const bool xin = m0 + r < M, win = n0 + r < N;
+    if (VEC) {
+        // clamped addresses: all 16 loads are unconditional, so they issue
+        // back to back before anything waits; out-of-range ones are zeroed
+        // on the way into LDS
+        const int kch = K >> 3;
+        const unsigned short* xr = x + (int64_t)min(m0 + r, M - 1) * K;
+        const unsigned short* wr = w + (int64_t)min(n0 + r, N - 1) * K;
+        u16x8 vx[8], vw[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = min(c16 + 16 * j, kch - 1);
+            vx[j] = *reinterpret_cast<const u16x8*>(xr + c * 8);
+            vw[j] = *reinterpret_cast<const u16x8*>(wr + c * 8);
+        }
+        const u16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = c16 + 16 * j;
+            if (c < nch) {
+                const bool kin = c < kch;
+                *reinterpret_cast<u16x8*>(xs + r * ld + c * 8) =
+                    (xin && kin) ? vx[j] : zero;
+                *reinterpret_cast<u16x8*>(ws + r * ld + c * 8) =
+                    (win && kin) ? vw[j] : zero;
+            }
+        }
+    } else {
+        for (int c = c16; c < nch; c += 16) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int k = c * 8 + e;
+                xs[r * ld + k] =
+                    (xin && k < K) ? x[(int64_t)(m0 + r) * K + k] : 0;
+                ws[r * ld + k] =
+                    (win && k < K) ? w[(int64_t)(n0 + r) * K + k] : 0;
+            }
+        }
+    }
+    // the bias value rides along with the panel loads
+    const int ocol = n0 + c16;
+    const float bv = (bias && tid < 64 && ocol < N) ? bias[ocol] : 0.f;
+    __syncthreads();
+    if (tid >= 64) return;
+    const int sub = tid & 15, half = tid >> 4;
+    const unsigned short* xa = xs + sub * ld + half * 8;
+    const unsigned short* wa = ws + sub * ld + half * 8;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    // eight k-steps' fragments are read ahead of their MFMAs, so the chain
+    // waits on LDS once per eight steps, not once per step
+    int k = 0;
+    for (; k + 256 <= Kp; k += 256) {
+        bf16x8 a[8], b[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            a[u] = *reinterpret_cast<const bf16x8*>(xa + k + 32 * u);
+            b[u] = *reinterpret_cast<const bf16x8*>(wa + k + 32 * u);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[u], b[u], acc, 0,
+                                                          0, 0);
+    }
+    for (; k < Kp; k += 32) {
+        bf16x8 a = *reinterpret_cast<const bf16x8*>(xa + k);
+        bf16x8 b = *reinterpret_cast<const bf16x8*>(wa + k);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+        int orow = m0 + half * 4 + rr;
+        if (orow < M && ocol < N) {
+            float v = acc[rr] + bv;
+            if (relu) v = v > 0.f ? v : 0.f;
+            yout[(int64_t)orow * N + ocol] = f2bf(v);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Multi-tensor fused Adam + multi-tensor grad zero: ONE launch over all
 // parameter tensors via a precomputed chunk table (built once per optimizer;
 // hipGraph replays touch no host state).
@@ -5015,14 +5135,69 @@ std::vector<torch::Tensor> conv_bwd_pair(torch::Tensor dy, torch::Tensor w,
     return {dx, dw32};
 }
 
+static bool aligned16(const torch::Tensor& t) {
+    return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0;
+}
+
+// Envelope of linear_panel_kernel (testable from Python like
+// conv_bwd_pair_ok): exactly linear_fwd's one-slab case, where it would
+// launch linear_splitk_kernel<1>. Ragged M / N / K are zero padded inside
+// the kernel; vec says whether the panels can be fetched with 16-B loads.
+static bool linear_fwd_panel_plan(const torch::Tensor& x,
+                                  const torch::Tensor& w, bool& vec) {
+    const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+    vec = (K % 8) == 0 && aligned16(x) && aligned16(w);
+    return M >= 1 && M <= 64 && N >= 1 && K >= 1 && K <= LP_KMAX;
+}
+
+bool linear_fwd_panel_ok(torch::Tensor x, torch::Tensor w) {
+    bool vec;
+    return x.is_cuda() && x.dim() == 2 && w.dim() == 2 &&
+           linear_fwd_panel_plan(x, w, vec);
+}
+
+template <bool VEC>
+static void launch_linear_panel(const torch::Tensor& x, const torch::Tensor& w,
+                                const float* bias, torch::Tensor& y, int M,
+                                int N, int K, bool relu, hipStream_t stream) {
+    // K near 1024 needs more dynamic LDS than the default limit: raise it
+    // once per device, on the first launch (warm-up, outside any capture)
+    static bool raised[64] = {};
+    const int dev = x.get_device();
+    if (dev >= 0 && dev < 64 && !raised[dev]) {
+        TORCH_CHECK(hipFuncSetAttribute(
+                        reinterpret_cast<const void*>(&linear_panel_kernel<VEC>),
+                        hipFuncAttributeMaxDynamicSharedMemorySize,
+                        LP_SMEM_MAX) == hipSuccess,
+                    "linear_panel_kernel: cannot raise the dynamic LDS limit");
+        raised[dev] = true;
+    }
+    const int Kp = (K + 31) & ~31;
+    const size_t smem = (size_t)2 * 16 * (Kp + LP_PAD) * sizeof(unsigned short);
+    dim3 grid(ceildiv(M, 16), ceildiv(N, 16), 1);
+    hipLaunchKernelGGL((linear_panel_kernel<VEC>), grid, dim3(TPB), smem,
+                       stream, bf_ptr(x), bf_ptr(w), bias, bf_ptr_mut(y), M, N,
+                       K, relu ? 1 : 0);
+}
+
+// panel = false keeps the one-slab case on linear_splitk_kernel<1> (the
+// yardstick the panel kernel is compared against, HEFL_LIN_FWD_PANEL=0).
 torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b,
-                         bool relu) {
+                         bool relu, bool panel) {
     CHECK_GPU(x);
     TORCH_CHECK(x.is_contiguous() && w.is_contiguous());
     const int M = (int)x.size(0), K = (int)x.size(1), N = (int)w.size(0);
     auto stream = at::cuda::getCurrentCUDAStream();
     const float* bias = b.numel() ? b.data_ptr<float>() : nullptr;
     auto y = torch::empty({M, N}, x.options());
+    bool vec = false;
+    if (panel && linear_fwd_panel_plan(x, w, vec)) {
+        if (vec)
+            launch_linear_panel<true>(x, w, bias, y, M, N, K, relu, stream);
+        else
+            launch_linear_panel<false>(x, w, bias, y, M, N, K, relu, stream);
+        return y;
+    }
     if (M <= 64) {
         // slab count targets >= 256 blocks: K/4 left the cnn4 flatten
         // layer (K = 18432) at 64 blocks / 25% of the CUs (~440 GB/s)

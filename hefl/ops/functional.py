@@ -81,6 +81,12 @@ _HEAD_XENT = os.getenv("HEFL_HEAD_XENT", "1") != "0"
 # launches): dgrad and wgrad of a Dense layer in ONE launch (blockIdx.z
 # selects the role; bit-identical outputs).
 _LIN_PAIR = os.getenv("HEFL_LIN_PAIR", "1") != "0"
+# Whole-K panel forward (default ON, HEFL_LIN_FWD_PANEL=0 restores
+# linear_splitk_kernel<1>): linear_fwd's one-slab case (M <= 64, K <= 1024)
+# loads a tile's x and w panels into LDS with every load in flight at once,
+# then runs the same MFMA chain; bit-identical y
+# (tests/test_gpu_linear_vec.py).
+_LIN_FWD_PANEL = os.getenv("HEFL_LIN_FWD_PANEL", "1") != "0"
 # Pool fused into the conv forward epilogue (default ON, HEFL_CONV_POOL=0
 # restores conv2d_fwd + maxpool2x2_fwd): conv2d_relu_pool_fwd enumerates
 # the implicit-GEMM rows pool-window-major so the 2x2 max is three register
@@ -376,6 +382,12 @@ def conv_bwd_pair_ok(dy, w, pad: int, H: int, W: int) -> bool:
     return bool(dy.is_cuda and _C().conv_bwd_pair_ok(dy, w, pad, H, W))
 
 
+def linear_fwd_panel_ok(x, w) -> bool:
+    """Whether linear_fwd(x[M,K], w[N,K], ...) runs the whole-K panel kernel
+    (cnn.hip linear_fwd_panel_plan): its one-slab case, M <= 64, K <= 1024."""
+    return bool(x.is_cuda and _C().linear_fwd_panel_ok(x, w))
+
+
 # ---------------------------------------------------------------------------
 # Linear (Dense): y = x @ w^T + b, optional fused ReLU.
 # ---------------------------------------------------------------------------
@@ -389,7 +401,7 @@ class _LinearFn(torch.autograd.Function):
         if x.is_cuda:
             wb = _gpu_dtype(w)
             bb = b.detach().float() if b is not None else torch.empty(0, device=x.device)
-            y = _C().linear_fwd(x, wb, bb, relu)
+            y = _C().linear_fwd(x, wb, bb, relu, _LIN_FWD_PANEL)
             ctx.save_for_backward(x, wb, y)
         else:
             y = F.linear(x.float(), w, b)
@@ -443,9 +455,10 @@ class _DenseHead2Fn(torch.autograd.Function):
     def forward(ctx, x, w1, b1, w2, b2):
         w1b, w2b = _gpu_dtype(w1), _gpu_dtype(w2)
         xc = x.contiguous()
-        h1 = _C().linear_fwd(xc, w1b.contiguous(), b1.detach().float(), True)
+        h1 = _C().linear_fwd(xc, w1b.contiguous(), b1.detach().float(), True,
+                             _LIN_FWD_PANEL)
         logits = _C().linear_fwd(h1, w2b.contiguous(), b2.detach().float(),
-                                 False)
+                                 False, _LIN_FWD_PANEL)
         ctx.save_for_backward(xc, h1, w1b, w2b)
         return logits
 
@@ -560,7 +573,8 @@ class _DenseHead2XentFn(torch.autograd.Function):
         w1b, w2b = _gpu_dtype(w1).contiguous(), _gpu_dtype(w2).contiguous()
         xc = x.contiguous()
         empty = torch.empty(0, device=x.device)
-        h1 = _C().linear_fwd(xc, w1b, b1.detach().float(), True)
+        h1 = _C().linear_fwd(xc, w1b, b1.detach().float(), True,
+                             _LIN_FWD_PANEL)
         logits, probs, loss = _C().head_xent_fwd(
             h1, w2b, b2.detach().float(), labels,
             acc_loss if acc_loss is not None else empty,
